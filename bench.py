@@ -10,6 +10,13 @@ launch): two streams, or four for short frames (--streams auto, the default: a f
 0.6 ms, or too few rays to fill the chip's resident waves); --streams 1 runs them back to back.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--camera B]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K frames, writes the last timed frame with
+--dump-outputs, and prints the JSON line: the headline rate with the figures that come out of
+the timed frames themselves (kernel, roofline, dist). --full adds the legs that take runs of
+their own after the timed frames: the display-only resident frames, the host-buffer frames and
+batch calls (one of them in a fresh child process), and the CPU baseline with its parity check.
 
 N > 1 is launched by torch.distributed.run, one process per GPU. Every frame is an image
 split into cyclic row-block shards (block b -> shard b % S); rank r renders shard r and rank 0
@@ -25,7 +32,13 @@ bhrt/dist_frame.py):
   traces it at the reference's Halton sub-pixel offset k and one RCCL reduce averages the
   colour (trace_pixel's sample average, raytracer.c:1096-1164).
 
-The JSON line also carries:
+--dump-outputs DIR writes what the last timed frame left on rank 0, as DIR/<field>.npy: every
+field of its per-ray SoA (float64; rgba8 as float32 [rays, 4]) and, at N > 1, the gathered
+image fields as DIR/image_<field>.npy. Above DUMP_BUDGET_BYTES in all, the same seeded sample
+of rays is written for every field, its flat ray indices as DIR/sample_index.npy. The frame is
+synthetic and deterministic, so two builds run with the same arguments compare ray for ray.
+
+The JSON line also carries (cpu_baseline with --full only):
   roofline      FP64 VALU roofline of the trace kernel: algorithmic FLOPs (SURVEY.md 8(a):
                 117 per RK4 iteration + 35 per a=0 derivative stage + 4 per far-field stage;
                 368 per RKF45 attempt + the same stage costs; a Kerr stage's accelerations are
@@ -133,6 +146,9 @@ AUTO_SHORT_MS = 0.6
 # many ms of back-to-back frames and the timed region follows after one sync.
 WARM_MS = float(os.environ.get("BHRT_BENCH_WARM_MS", "200"))
 AUTO_FILL_RAYS = 256 * 4 * 4 * 64  # 4 waves per SIMD x 4 SIMDs x 256 CUs x 64 lanes
+# --dump-outputs: at most this many bytes of .npy data in all (a seeded ray sample above it)
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 0
 
 
 def parse():
@@ -143,14 +159,24 @@ def parse():
     p.add_argument("--config", default="C2")
     p.add_argument("--camera", default="B")
     p.add_argument("--refill", type=int, default=None)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed frames, write the last one as DIR/<field>.npy (rank "
+                        "0's per-ray SoA, float64 / float32; at N > 1 also the gathered "
+                        "image_<field>.npy), at most DUMP_BUDGET_BYTES in all: above that a "
+                        "seeded sample of the rays, indices in DIR/sample_index.npy")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed frames also run the side legs: display-only resident "
+                        "frames, host-buffer frames and batch calls, the CPU baseline and its "
+                        "parity check (--no-host-path / --no-cpu-baseline leave one out)")
     p.add_argument("--cpu-rows-stride", type=int, default=None,
-                   help="CPU baseline samples every k-th row of the rendered shard (default "
-                        "per config, ~1-3 s on 16 cores: CPU_ROWS_STRIDE)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="--full: CPU baseline samples every k-th row of the rendered shard "
+                        "(default per config, ~1-3 s on 16 cores: CPU_ROWS_STRIDE)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baseline")
     p.add_argument("--no-host-path", action="store_true",
-                   help="skip the extra legs after the timed frames: host-buffer frames and "
-                        "the display-only resident frames (their launches would mix into a "
-                        "profiler's per-launch kernel averages)")
+                   help="--full without the host-buffer frames and the display-only resident "
+                        "frames (their launches would mix into a profiler's per-launch kernel "
+                        "averages)")
     p.add_argument("--fields", choices=("all", "display"), default="all",
                    help="what each timed frame writes: every SoA field + rgba8 (100 B/ray, "
                         "default; the CPU baseline compares them) or the visualizer's display "
@@ -227,7 +253,9 @@ def main():
     args = parse()
     if args.batch_fresh_child:
         return batch_fresh_child(args)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if not args.full:  # a plain run: the timed frames only, none of the side legs
+        args.no_host_path = args.no_cpu_baseline = True
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     auto = args.streams == "auto"
@@ -434,7 +462,9 @@ def main():
 
     if order_keep is not None:
         lib.set_claim_order(None, 0)
-    rays_all = float(rays_frame) * args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame, world)
+    rays_all =float(rays_frame) * args.steps
     mrays = rays_all / elapsed / 1e6
     launches = max(st["launches"], 1)
     kern_ms = st["kernel_ms"] / launches
@@ -465,7 +495,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "ms_per_step": round(elapsed / args.steps * 1e3, 6),
         "higher_is_better": True,
         "scaling": "strong" if c.scaling == "strong" else "weak",
         "vs_baseline": None,
@@ -576,6 +606,44 @@ def main():
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, frame, world):
+    """The last timed frame as rank 0 holds it (dist_frame.Assembled), one .npy per field:
+    `local` (the per-ray SoA of rank 0's shard, every field the frame wrote) as <field>.npy and,
+    at N > 1, `image` (the gathered fields, [H, W]) as image_<field>.npy. Doubles and the int32
+    fields as float64 (exact), rgba8 as float32 [rays, 4]. Over DUMP_BUDGET_BYTES in all, every
+    field keeps the same DUMP_SEED sample of its rays (sorted flat indices: sample_index.npy for
+    `local`, image_sample_index.npy for `image`), the budget split by the two sets' sizes."""
+    os.makedirs(directory, exist_ok=True)
+    sets = [("", frame.local)] + ([("image_", frame.image)] if world > 1 else [])
+
+    def ray_bytes(t):  # per ray, as written
+        return 4 * t.shape[-1] if t.dtype == torch.uint8 else 8
+
+    def rays_of(fields):
+        t = next(iter(fields.values()))
+        return t.shape[0] * t.shape[1]
+
+    total = sum(rays_of(fs) * sum(ray_bytes(t) for t in fs.values()) for _, fs in sets)
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for prefix, fs in sets:
+        n = rays_of(fs)
+        idx = None
+        if keep < 1.0:
+            per_ray = sum(ray_bytes(t) for t in fs.values())
+            count = int(n * keep * per_ray / (per_ray + 8))  # (+ 8: the index itself)
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, count, replace=False))
+            np.save(os.path.join(directory, prefix + "sample_index.npy"),
+                    pick.astype(np.float64))
+            idx = torch.from_numpy(pick).to(next(iter(fs.values())).device)
+        for f, t in fs.items():
+            flat = t.reshape(n, -1) if t.dtype == torch.uint8 else t.reshape(n)
+            if idx is not None:
+                flat = flat.index_select(0, idx)
+            a = flat.cpu().numpy()
+            np.save(os.path.join(directory, prefix + f + ".npy"),
+                    a.astype(np.float32 if a.dtype == np.uint8 else np.float64))
 
 
 def render_stream(device):

@@ -46,6 +46,17 @@ def test_gpus_1_runs_in_process():
                       "master_port": None, "device": 0}]
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    """--full and --dump-outputs DIR parse; nothing is written before the timed frames (the dry
+    run stops ahead of them)."""
+    out = tmp_path / "dump"
+    p, lines = _run("--gpus", "1", "--steps", "1", "--warmup", "0", "--full",
+                    "--dump-outputs", str(out))
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert [x["rank"] for x in lines] == [0]
+    assert not out.exists()
+
+
 def test_rehearsal_maps_every_rank_to_gpu_0():
     p, lines = _run("--gpus", "2", env_extra={"BHRT_BENCH_SHARE_DEVICE": "1"})
     assert p.returncode == 0, p.stderr[-3000:]

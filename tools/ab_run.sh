@@ -11,6 +11,6 @@ if [ -n "$TEST_VARIANTS" ]; then VARIANTS="$TEST_VARIANTS" bash tools/ab_tests.s
 VARIANTS="${VARIANTS:-base}" ROUNDS=${ROUNDS:-2} bash tools/ab.sh || exit 1
 for v in ${CPU_VARIANTS:-base}; do
   if [ $v = base ]; then lib=raytracing-engine-in-c_amd/libbhrt.so; else lib=raytracing-engine-in-c_amd/ab/libbhrt_$v.so; fi
-  BHRT_LIB=$lib timeout -k 10 300 python bench.py --config ${CFG:-C2} --steps 3 --warmup 1 --no-host-path > gpurun_out/ab/cpu_$v.json 2>/dev/null || exit 1
-  python3 -c "import json; d=json.load(open('gpurun_out/ab/cpu_$v.json')); print('cpu-parity $v', d['value'], d['class_mismatch'], d['max_rel_dhit'])"
+  BHRT_LIB=$lib timeout -k 10 300 python bench.py --config ${CFG:-C2} --steps 3 --warmup 1 --full --no-host-path 2>/dev/null \
+    | python3 -c "import json, sys; d=json.loads(sys.stdin.read()); print('cpu-parity $v', d['value'], d['class_mismatch'], d['max_rel_dhit'])" || exit 1
 done

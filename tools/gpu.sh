@@ -8,8 +8,8 @@
 # Steps (outputs under gpurun_out/$TAG, TAG defaults to "s"):
 #   tests          python -m pytest tests -m gpu (-x, per-test timeout)
 #   smoke          __graft_entry__.smoke()
-#   bench          the default bench line (bench.py, no flags)
-#   rocprof        the default bench line under rocprofv3 --kernel-trace --stats (+ trace span)
+#   bench          the full bench line (bench.py --full: every side leg)
+#   rocprof        the full bench line under rocprofv3 --kernel-trace --stats (+ trace span)
 #   rocprof_timed  the timed frames alone under rocprofv3: busy span per dispatch vs the line's avg_ms
 #   bench_all      bench.py --config C1..C5 ($CONFIGS), N = 1
 #   plan           every shard of the 8-GPU plans of $PLAN_CFGS (tools/plan_shards.sh) + summary
@@ -39,12 +39,12 @@ for step in "$@"; do
       || fail smoke $OUT/smoke.log
     tail -n 1 $OUT/smoke.log ;;
   bench)
-    timeout -k 10 400 python bench.py $BENCH_ARGS > $OUT/bench_default.json 2> $OUT/bench_default.err \
+    timeout -k 10 400 python bench.py --full $BENCH_ARGS > $OUT/bench_default.json 2> $OUT/bench_default.err \
       || fail bench $OUT/bench_default.err
     cat $OUT/bench_default.json ;;
   rocprof)
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_default -o run --output-format csv \
-      -- python bench.py $BENCH_ARGS > $OUT/bench_default_prof.json 2> $OUT/prof_default.err \
+      -- python bench.py --full $BENCH_ARGS > $OUT/bench_default_prof.json 2> $OUT/prof_default.err \
       || fail rocprof $OUT/prof_default.err
     python tools/trace_span.py $(find $OUT/prof_default -name "*kernel_trace.csv" | head -1) --skip 2 \
       > $OUT/trace_span_default.txt || true

@@ -6,7 +6,7 @@ OUT=gpurun_out/hostk; mkdir -p $OUT
 for cfg in ${CONFIGS:-C2}; do
   for k in ${CHUNKS:-1 2 3 4 8}; do
     for stg in "" 1; do
-      BHRT_HOST_CHUNKS=$k BHRT_HOST_REGISTER=$stg timeout -k 10 300 python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$cfg.$k.$stg.json 2> $OUT/$cfg.$k.$stg.err || { echo "$cfg $k failed"; tail -5 $OUT/$cfg.$k.$stg.err; exit 1; }
+      BHRT_HOST_CHUNKS=$k BHRT_HOST_REGISTER=$stg timeout -k 10 300 python bench.py --config $cfg --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/$cfg.$k.$stg.json 2> $OUT/$cfg.$k.$stg.err || { echo "$cfg $k failed"; tail -5 $OUT/$cfg.$k.$stg.err; exit 1; }
       python3 -c "import json; d=json.load(open('$OUT/$cfg.$k.$stg.json'))['host_path']; print('$cfg chunks=$k register=${stg:-0}', d)"
     done
   done
