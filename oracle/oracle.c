@@ -99,7 +99,7 @@ void orc_initialize_black_hole_params(BlackHoleParams* bh, double mass, double s
     bh->isco_radius = isco_radius(bh);
 }
 
-/* ---- knife-edge margins; off unless orc_render_frame_margin runs ----
+/* ---- knife-edge margins; off unless an orc_*_margin driver runs ----
  * For every DISCONTINUOUS decision a ray takes (step-size schedule, far-field switch,
  * horizon and distance exits, RKF45 accept, the pole clamp's sign, the disk test's
  * |denominator| threshold, t sign and radii), the relative distance of the tested value from
@@ -701,9 +701,10 @@ int orc_render_frame_margin(const BlackHoleParams* bh, const AccretionDiskParams
     return render_frame(bh, disk, cfg, cam, W, H, rows, method, flags, out, margin, nthreads);
 }
 
-int orc_trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
-                   const AccretionDiskParams* disk, const SimulationConfig* cfg,
-                   IntegrationMethod method, int flags, const bhrt_frame_soa* out, int nthreads) {
+static int trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
+                      const AccretionDiskParams* disk, const SimulationConfig* cfg,
+                      IntegrationMethod method, int flags, const bhrt_frame_soa* out,
+                      double* margin, int nthreads) {
     if (!rays || !bh || !cfg || !out || n <= 0) return -1;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
@@ -713,10 +714,26 @@ int orc_trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
 #pragma omp parallel for schedule(dynamic, 16)
     for (int i = 0; i < n; i++) {
         RayTraceHit h;
+        g_mg_on = margin != NULL;
         trace_one(&rays[i], bh, disk, cfg, method, &h);
+        if (margin) margin[i] = g_mg_result;
+        g_mg_on = 0;
         double rgb[3]; /* colour sees Ray.direction as given, like the disk test */
         frame_colour(h.result, &h.hit_position, &rays[i].direction, bh, disk, flags, rgb);
         store(out, i, &h, rgb);
     }
     return 0;
+}
+
+int orc_trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
+                   const AccretionDiskParams* disk, const SimulationConfig* cfg,
+                   IntegrationMethod method, int flags, const bhrt_frame_soa* out, int nthreads) {
+    return trace_rays(rays, n, bh, disk, cfg, method, flags, out, NULL, nthreads);
+}
+
+int orc_trace_rays_margin(const Ray* rays, int n, const BlackHoleParams* bh,
+                          const AccretionDiskParams* disk, const SimulationConfig* cfg,
+                          IntegrationMethod method, int flags, const bhrt_frame_soa* out,
+                          double* margin, int nthreads) {
+    return trace_rays(rays, n, bh, disk, cfg, method, flags, out, margin, nthreads);
 }

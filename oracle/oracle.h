@@ -62,6 +62,11 @@ int orc_render_frame_margin(const BlackHoleParams* bh, const AccretionDiskParams
 int orc_trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
                    const AccretionDiskParams* disk, const SimulationConfig* cfg,
                    IntegrationMethod method, int flags, const bhrt_frame_soa* out, int nthreads);
+/* the same batch, plus each ray's knife-edge margin */
+int orc_trace_rays_margin(const Ray* rays, int n, const BlackHoleParams* bh,
+                          const AccretionDiskParams* disk, const SimulationConfig* cfg,
+                          IntegrationMethod method, int flags, const bhrt_frame_soa* out,
+                          double* margin, int nthreads);
 /* rows of a shard (same rule as bhrt_shard_rows) and local row j -> image row */
 /* update_particles (particle_sim.c:505-566) applied `steps` times to ps[0, count) */
 void orc_update_particles(Particle* ps, int count, const BlackHoleParams* bh,

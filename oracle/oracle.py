@@ -89,6 +89,20 @@ class Checker:
         assert rc == 0
         return arrays
 
+    def trace_rays_margin(self, rays, bh, dk, cfg, method=abi.INTEGRATOR_RK4, flags=0, threads=0,
+                          fields=abi.SOA_FIELDS):
+        """trace_rays plus every ray's knife-edge margin (oracle only): (arrays, margin)."""
+        fn = self.lib.orc_trace_rays_margin
+        fn.argtypes = _RAYS_ARGS[:-1] + [C.c_void_p, C.c_int]
+        fn.restype = C.c_int
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+        arrays, soa = abi.alloc_soa(len(rays), fields)
+        margin = np.empty(len(rays), dtype=np.float64)
+        rc = fn(rays.ctypes.data, len(rays), C.byref(bh), C.byref(dk) if dk else None,
+                C.byref(cfg), method, flags, C.byref(soa), margin.ctypes.data, threads)
+        assert rc == 0
+        return arrays, margin
+
 
 def _shard_rows(H, rows):
     if rows is None or rows.num_shards <= 1:

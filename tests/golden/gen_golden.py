@@ -556,6 +556,60 @@ def shader_data():
          null_rc=np.array(null_rc, dtype=np.int64))
 
 
+def save_fixed(name, arrays):
+    """An .npz (deflated, np.load reads it) whose bytes depend on the arrays alone:
+    np.savez_compressed stamps every member with the current time."""
+    import io
+    import zipfile
+    path = os.path.join(HERE, name + ".npz")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(v), version=(1, 0),
+                                      allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+    print("wrote", name, os.path.getsize(path), "bytes", file=sys.stderr)
+
+
+def sweep():
+    """The scene sweep (tests/sweep_scenes.py): for every scene the reference's outputs on the
+    181 edge rays of rays_rk4_disk.npz, and for sweep_scenes.FRAME_FIXTURES one 48x27 frame.
+    Inputs are stored by scene name only (the table is the source of truth); outputs are the
+    fields conftest.compare reads, result/steps as int32."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import sweep_scenes as sw
+    with np.load(os.path.join(HERE, "rays_rk4_disk.npz")) as z:
+        r = z["rays"]
+    rays = np.zeros(len(r), dtype=abi.RAY_DTYPE)
+    rays["origin"], rays["direction"] = r[:, 0:3], r[:, 3:6]
+
+    def pinned(out, method):
+        fields = ["result", "steps", "hit_x", "hit_y", "hit_z", "distance", "time_dilation",
+                  "rgb_r", "rgb_g", "rgb_b"]
+        if method != abi.INTEGRATOR_RK4:  # (conftest.sky_pinned)
+            fields += ["sky_x", "sky_y", "sky_z"]
+        return {f: out[f].astype(np.int32) if f in ("result", "steps") else out[f]
+                for f in fields}
+
+    names = list(sw.SCENES)
+    for g in range(0, len(names), sw.RAY_GROUP):
+        arrays = {}
+        for name in names[g:g + sw.RAY_GROUP]:
+            bh, dk, cfg, method, flags, _ = sw.scene(name)
+            out = REF.trace_rays(rays, bh, dk, cfg, method, flags)
+            for f, v in pinned(out, method).items():
+                arrays[f"{name}.{f}"] = v
+        save_fixed(f"sweep_rays_{g // sw.RAY_GROUP}", arrays)
+    for name in sw.FRAME_FIXTURES:
+        bh, dk, cfg, method, flags, _ = sw.scene(name)
+        cam = sw.camera(sw.fixture_camera(name))
+        out = REF.render_frame(bh, dk, cfg, cam, sw.W, sw.H, method, flags)
+        save_fixed(f"sweep_frame_{name}", pinned(out, method))
+
+
 if __name__ == "__main__":
     if sys.argv[1:]:  # regenerate only the named fixture groups
         for name in sys.argv[1:]:
@@ -570,3 +624,4 @@ if __name__ == "__main__":
     paths()
     edge_rays()
     frames()
+    sweep()
