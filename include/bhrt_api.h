@@ -322,6 +322,50 @@ int bhrt_render_frame(const BlackHoleParams* blackhole, const AccretionDiskParam
                       int height, IntegrationMethod method, int flags,
                       const bhrt_frame_soa* host_out);
 
+/* ---- supersampled frames: every pixel is trace_pixel's sample average ---- */
+#define BHRT_SS_MAX_SAMPLES 64
+
+/* trace_pixel's sample count and sub-pixel offsets (raytracer.c:1066-1108, 868-932) for
+ * these parameters: writes offset_x/y[0..count) and returns count (>= 1), or -1.
+ * count = ss ? ss->samples_per_pixel : 1, or with as->enable_adaptive min_samples +
+ * (int)((max_samples - min_samples) * 1.0) capped at max_samples (the reference's edge factor is
+ * fixed at 1). Sample s lies at generate_jittered_position(s, ss->samples_per_pixel, ...) where
+ * ss->samples_per_pixel > 1, else at the centre (0.5, 0.5) -- with the reference's quirks: the
+ * grid is (int)sqrt(spp) wide (the fifth sample of a "2x2" grid lies at (0.25, 1.25), outside
+ * the pixel), Halton sample 0 is (0, 0), JITTER_BLUE_NOISE is Halton, jitter_strength != 1
+ * scales about the centre. -1 for JITTER_RANDOM with more than one sample per pixel (rand() per
+ * pixel: not reproducible), a count below 1 or above BHRT_SS_MAX_SAMPLES, or above capacity. */
+int bhrt_sample_offsets(const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
+                        double* offset_x, double* offset_y, int capacity);
+
+/* (A shard of) a camera frame in which every pixel is trace_pixel(px, py, ..., ss, as), for any
+ * method and flags: DEVICE buffers, asynchronous on hip_stream (NULL: ordered like the legacy
+ * default stream, exactly as bhrt_render_frame_device). Of device_out only result (the class of
+ * sample 0, trace_pixel's return value), rgb_r/g/b (all three), rgba32f and rgba8 may be
+ * non-NULL. The pixel colour is ((...((0.0 + c_0) + c_1) + ...) + c_{S-1}) / S per channel in
+ * IEEE double, trace_pixel's accumulation order, with no contraction and no atomics: a pure
+ * function of the pixel's samples, the same bits run to run, on any stream and in any shard
+ * split; one NaN sample makes the pixel NaN (rgba8 255). The S samples of all pixels are traced
+ * by one launch of rays * S rays (bhrt_stats.rays counts them; bhrt_set_claim_order does not
+ * apply) into per-stream scratch of about 228 B per sample ray -- 52 B of directions, colour
+ * and class on top of the 176 B of launch scratch every ray has -- i.e. 1.9 GB for a 1920x1080
+ * frame of 4 samples. Returns 0, or -1 (nothing written) for a bad bhrt_sample_offsets case,
+ * camera->use_offset != 0, any other non-NULL field, rays * S > INT_MAX, or an allocation or
+ * HIP failure (bhrt_last_error). */
+int bhrt_render_frame_ss_device(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                                const SimulationConfig* config, const bhrt_camera* camera,
+                                int width, int height, const bhrt_rows* rows,
+                                IntegrationMethod method, int flags,
+                                const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
+                                const bhrt_frame_soa* device_out, void* hip_stream);
+
+/* The same whole frame into HOST arrays, on the current device; returns when it is complete. */
+int bhrt_render_frame_ss(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                         const SimulationConfig* config, const bhrt_camera* camera, int width,
+                         int height, IntegrationMethod method, int flags,
+                         const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
+                         const bhrt_frame_soa* host_out);
+
 /* Asynchronous form of bhrt_render_frame: queues the frame and returns a ticket (> 0) in
  * *ticket; the host arrays receive the frame through libbhrt's pinned staging (caller memory
  * is never page-locked) and must not be read or freed before bhrt_frame_wait(ticket) returns. Three

@@ -53,6 +53,20 @@ _PROTOS = {
                                            _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
                                            C.c_int, C.c_int, C.c_int, _P(abi.FrameSoA), C.c_int,
                                            C.c_int, C.c_void_p]),
+    "bhrt_sample_offsets": (C.c_int, [_P(abi.SupersamplingParams),
+                                      _P(abi.AdaptiveSamplingParams), C.c_void_p, C.c_void_p,
+                                      C.c_int]),
+    "bhrt_render_frame_ss_device": (C.c_int, [_P(abi.BlackHoleParams),
+                                              _P(abi.AccretionDiskParams),
+                                              _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
+                                              C.c_int, _P(abi.Rows), C.c_int, C.c_int,
+                                              _P(abi.SupersamplingParams),
+                                              _P(abi.AdaptiveSamplingParams), _P(abi.FrameSoA),
+                                              C.c_void_p]),
+    "bhrt_render_frame_ss": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.AccretionDiskParams),
+                                       _P(abi.SimulationConfig), _P(abi.Camera), C.c_int, C.c_int,
+                                       C.c_int, C.c_int, _P(abi.SupersamplingParams),
+                                       _P(abi.AdaptiveSamplingParams), _P(abi.FrameSoA)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -197,6 +211,44 @@ def render_frame_gather(bh, dk, cfg, cam, width, height, method, flags, soa, nde
                                            int(shards),
                                            C.c_void_p(stream) if stream else None),
            "bhrt_render_frame_gather")
+
+
+SS_MAX_SAMPLES = 64  # BHRT_SS_MAX_SAMPLES
+SS_FIELDS = ("result", "rgb_r", "rgb_g", "rgb_b", "rgba32f", "rgba8")
+
+
+def sample_offsets(ss, as_=None):
+    """bhrt_sample_offsets: trace_pixel's sub-pixel offsets for these SupersamplingParams /
+    AdaptiveSamplingParams (either may be None), as a float64 array [count, 2]."""
+    ox = np.zeros(SS_MAX_SAMPLES)
+    oy = np.zeros(SS_MAX_SAMPLES)
+    n = load().bhrt_sample_offsets(_ptr(ss), _ptr(as_), ox.ctypes.data, oy.ctypes.data,
+                                   SS_MAX_SAMPLES)
+    if n < 0:
+        raise BhrtError(f"bhrt_sample_offsets failed: {last_error()}")
+    return np.stack([ox[:n], oy[:n]], axis=1)
+
+
+def render_frame_ss_device(bh, dk, cfg, cam, width, height, rows, method, flags, ss, as_, soa,
+                           stream):
+    """bhrt_render_frame_ss_device: (a shard of) a frame of trace_pixel sample averages into
+    device SoA buffers (result, rgb_*, rgba32f, rgba8), asynchronous on a hipStream_t (int handle
+    or None)."""
+    _check(load().bhrt_render_frame_ss_device(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width,
+                                              height, _ptr(rows), method, flags, _ptr(ss),
+                                              _ptr(as_), C.byref(soa),
+                                              C.c_void_p(stream) if stream else None),
+           "bhrt_render_frame_ss_device")
+
+
+def render_frame_ss(bh, dk, cfg, cam, width, height, method=abi.INTEGRATOR_RK4, flags=0, ss=None,
+                    as_=None, fields=SS_FIELDS):
+    """bhrt_render_frame_ss into host numpy arrays (the current device)."""
+    arrays, soa = abi.alloc_soa(width * height, fields)
+    _check(load().bhrt_render_frame_ss(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
+                                       method, flags, _ptr(ss), _ptr(as_), C.byref(soa)),
+           "bhrt_render_frame_ss")
+    return arrays
 
 
 def set_claim_order(d_order_ptr, n):

@@ -189,6 +189,9 @@ typedef struct {
     hipEvent_t g_done, g_copied, g_wait;
     int g_wait_pending;
     unsigned long long peer_on; /* bit d: peer access to device d enabled from this device */
+    /* bhrt_render_frame_ss (supersample.c): device outputs of a host-array frame */
+    void* d_ss;
+    size_t cap_ss;
 } devctx_t;
 
 static _Thread_local devctx_t* g_ctx[BHRT_MAX_DEV];
@@ -2392,6 +2395,53 @@ RayTraceResult trace_pixel(int px, int py, int W, int H, const Vector3D* cam_pos
     color_out[1] /= samples;
     color_out[2] /= samples;
     return result;
+}
+
+/* ======================================================================================= */
+/* what supersample.c builds on (bhrt_host.h): wrappers only, no behaviour of their own     */
+/* ======================================================================================= */
+void* bhrt_hook_ctx(void) { return ctx_get(current_device()); }
+
+void* bhrt_hook_ctx_stream(void* ctx) {
+    devctx_t* c = (devctx_t*)ctx;
+    return ctx_streams(c) == 0 ? (void*)c->stream : NULL;
+}
+
+void* bhrt_hook_scratch(void* ctx, void* stream, size_t bytes) {
+    return stream_scratch((devctx_t*)ctx, (hipStream_t)stream, bytes);
+}
+
+void* bhrt_hook_ss_buffer(void* ctx, size_t bytes) {
+    devctx_t* c = (devctx_t*)ctx;
+    return ensure(&c->d_ss, &c->cap_ss, bytes ? bytes : 256, 0) ? NULL : c->d_ss;
+}
+
+int bhrt_hook_null_unordered(void) { return null_unordered(); }
+
+int bhrt_hook_null_fence(void* ctx, int after) { return null_fence((devctx_t*)ctx, after); }
+
+int bhrt_hook_trace_dirs(const double* d_dirs, int n, const BlackHoleParams* bh,
+                         const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                         IntegrationMethod method, int flags, const bhrt_frame_soa* out,
+                         void* stream, const Vector3D* origin) {
+    return trace_rays_device(NULL, d_dirs, n, bh, dk, cfg, method, flags, out, stream, origin);
+}
+
+void bhrt_hook_fill_camera(bhrt_kparams* kp, const BlackHoleParams* bh,
+                           const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                           IntegrationMethod method, int flags, const bhrt_camera* cam, int W,
+                           int H) {
+    fill_scene(kp, bh, dk, cfg, method, flags);
+    fill_camera(kp, cam, W, H);
+}
+
+int bhrt_hook_colour_fused(int method, int has_disk, int spin) {
+    return colour_fused(method, has_disk, spin);
+}
+
+void bhrt_hook_jitter(int sample, int spp, JitterMethod jm, double strength, double* ox,
+                      double* oy) {
+    jitter(sample, spp, jm, strength, ox, oy);
 }
 
 /* ======================================================================================= */

@@ -141,6 +141,32 @@ typedef struct {
                              build records per-wave stamps under it; unused otherwise) */
 } bhrt_kparams;
 
+/* Supersampled camera frames (supersample.c; geodesic.hip k_ss_rays, k_ss_resolve): two
+ * elementwise kernels around ONE shared-origin trace of n * samples rays. The sample rays are
+ * sample-major -- ray s * n + p is shard pixel p (camera_dir's index) at sample s -- so sample
+ * plane s is exactly the frame at offset s. k_ss_rays is launched once per sample, the sample's
+ * offset by value in the argument block's camera, and reads that camera in place as k_trace and
+ * k_colour read theirs: with the offset patched into a local copy of the block hipcc contracted
+ * camera_dir's squared length in another order (x*x first instead of y*y), one ulp off the
+ * camera path's directions. */
+typedef struct {
+    bhrt_camera_k cam;    /* basis, image plane and row shard (fill_camera); off_x/off_y: the
+                             sample's sub-pixel offset */
+    int n, sample;        /* shard pixels; the sample s: this launch writes rays [s n, s n + n) */
+    double* dirs;         /* [n * samples][3] packed directions (the trace's kp.dirs) */
+} bhrt_ss_rays_k;
+
+typedef struct {
+    int n, samples;
+    const int32_t* result;      /* [samples][n] sample planes written by the trace */
+    const double *r, *g, *b;
+    bhrt_frame_soa out;         /* result, rgb_r/g/b, rgba32f, rgba8; NULL fields skipped */
+} bhrt_ss_resolve_k;
+
+/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream);
+int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream);
+
 /* update_particles (particle_sim.c:505-566) constants, from the BlackHoleParams and
  * SimulationConfig of the call */
 typedef struct {

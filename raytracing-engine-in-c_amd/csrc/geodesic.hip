@@ -1901,6 +1901,44 @@ __global__ __launch_bounds__(256) void k_colour(const bhrt_kparams kp) {
     }
 }
 
+// Supersampled frames (bhrt_kernel.h bhrt_ss_rays_k): the directions of one sample's rays, one
+// lane per pixel. camera_dir itself on the argument block's camera, which carries the sample's
+// offset in place of the camera's: the row shard mapping and the direction arithmetic are the
+// camera path's own, and so are the directions' bits (test_gpu_supersample.py).
+__global__ __launch_bounds__(256) void k_ss_rays(const bhrt_ss_rays_k a) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.n) return;  // (the last workgroup's partial wave)
+    double dx, dy, dz;
+    camera_dir(a.cam, (int)p, dx, dy, dz);
+    double* d = a.dirs + ((size_t)a.sample * (size_t)a.n + (size_t)p) * 3;
+    d[0] = dx;
+    d[1] = dy;
+    d[2] = dz;
+}
+
+// trace_pixel's average (raytracer.c:1131-1164), one lane per pixel: the S sample colours added
+// in sample order from 0.0 and divided by S, as IEEE operations (no contraction), then the
+// outputs exactly as store_colour converts them; the class is sample 0's. Sample plane s is
+// contiguous, so every load and store of a wave is one contiguous run.
+__global__ __launch_bounds__(256) void k_ss_resolve(const bhrt_ss_resolve_k a) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.n) return;  // (the last workgroup's partial wave)
+    double r = 0.0, g = 0.0, b = 0.0;
+    for (int s = 0; s < a.samples; s++) {
+        const size_t i = (size_t)s * (size_t)a.n + (size_t)p;
+        r = r + a.r[i];
+        g = g + a.g[i];
+        b = b + a.b[i];
+    }
+    const double ns = (double)a.samples;
+    r = r / ns;
+    g = g / ns;
+    b = b / ns;
+    store_colour(a.out, (int)p, r, g, b);
+    if (a.out.result) a.out.result[p] = a.result[p];
+}
+
 // integrate_photon_path with a recorded path (one ray, one lane). The output hit goes to
 // element 0 of kp.out; the path and the stored-point count to path / d_num.
 template <int METHOD, bool SPIN0>
@@ -2215,6 +2253,20 @@ extern "C" int bhrt_launch_path(const bhrt_kparams* kp, const double* o4, const 
         launch_path<INTEGRATOR_LEAPFROG>(*kp, o4, d3, d_path, max_positions, d_num, num_in, st);
         break;
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream) {
+    if (k->n <= 0 || k->sample < 0) return 0;
+    k_ss_rays<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
+                static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream) {
+    if (k->n <= 0 || k->samples <= 0) return 0;
+    k_ss_resolve<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
+                   static_cast<hipStream_t>(stream)>>>(*k);
     return (int)hipGetLastError();
 }
 
