@@ -393,6 +393,56 @@ int bhrt_trace_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
                     const AccretionDiskParams* disk, const SimulationConfig* config,
                     IntegrationMethod method, int flags, const bhrt_frame_soa* host_out);
 
+/* ---- batched photon paths: the polylines of n rays in one launch ---- */
+#define BHRT_PATHS_MAX_POSITIONS 65536
+
+typedef struct {
+    Vector3D* xyz;     /* [n][max_positions], ray-major: xyz + i*max_positions is ray i's polyline,
+                          laid out as integrate_photon_path's own path_positions array          */
+    float*    xyz32;   /* [n][max_positions][3], (float) of the same doubles: a GL vertex buffer  */
+    int32_t*  count;   /* [n] points stored for ray i (<= max_positions)                          */
+} bhrt_paths;          /* any pointer may be NULL: that output is not produced                    */
+
+/* The recorded paths of n DEVICE rays into DEVICE arrays, asynchronous on hip_stream (NULL:
+ * ordered like the legacy default stream, as for bhrt_trace_rays_device).
+ * The full path q_0 .. q_{m-1} of ray i:
+ *  - disk == NULL: what integrate_photon_path(origin with t = 0, direction, ..., method, ...)
+ *    stores with max_positions unbounded (raytracer.c:504-507, 643-646): the origin, then one
+ *    point per executed loop iteration -- the repeated points of a stuck RKF45 ray and of the
+ *    "not implemented" LEAPFROG / YOSHIDA integrators included (max_integration_steps == 0: the
+ *    origin alone);
+ *  - disk != NULL: trace_ray's view of it (raytracer.c:717-759): if segment h is the first
+ *    that hits the disk, q_0 .. q_{h-1} followed by the hit's hit_position (m = h + 1), else
+ *    the full path.
+ * every = e >= 1 keeps q_0, q_e, q_2e, ... and also q_{m-1} where (m - 1) % e != 0, so the end
+ * of the ray is always drawn. Of that list the first max_positions points are stored (the
+ * reference's own truncation) and count[i] is how many were; elements of xyz / xyz32 at or
+ * beyond count[i] are NOT written. xyz32 holds (float) of xyz's doubles.
+ * device_hits may be NULL; otherwise it receives what bhrt_trace_rays_device writes for the same
+ * rays, disk, method and flags = 0 -- result, steps, hit_*, distance, time_dilation and sky_*,
+ * bit for bit: the trace kernel's own launch, queued behind the path launch on the same stream
+ * (the points are the single-ray path kernel's bits instead, so the last point of a long ray
+ * and its hit_position may differ in their last digits); a non-NULL colour or display field is
+ * an error.
+ * Every element index into the path arrays is formed in size_t. bhrt_stats counts the path
+ * launch as a trace launch (rays, iterations, launches), and the hits' launch as another.
+ * Returns 0, or -1 with nothing written (bhrt_last_error): n <= 0; NULL device_rays, blackhole
+ * or config; max_positions < 1 or > BHRT_PATHS_MAX_POSITIONS; every < 1; device_paths NULL or
+ * all three of its pointers NULL; (long)n * max_positions > INT_MAX; a colour or display field
+ * in device_hits; a HIP failure. */
+int bhrt_trace_paths_device(const Ray* device_rays, int n, const BlackHoleParams* blackhole,
+                            const AccretionDiskParams* disk, const SimulationConfig* config,
+                            IntegrationMethod method, int max_positions, int every,
+                            const bhrt_paths* device_paths, const bhrt_frame_soa* device_hits,
+                            void* hip_stream);
+
+/* The same with HOST arrays on the current device; returns when they are complete. Host
+ * elements of xyz / xyz32 at or beyond count[i] keep what they held. */
+int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* blackhole,
+                     const AccretionDiskParams* disk, const SimulationConfig* config,
+                     IntegrationMethod method, int max_positions, int every,
+                     const bhrt_paths* host_paths, const bhrt_frame_soa* host_hits);
+
 /* Diagnostic: both forms of the trace kernel's RKF45 accept test (the division-free fast
  * form and the reference's literal quotient, geodesic.hip rkf45_accept) on n cases of DEVICE
  * arrays err[6n], scale[6n], tol[n]; d_out[2i] / d_out[2i+1] = the two decisions. Returns 0

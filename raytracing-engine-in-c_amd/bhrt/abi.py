@@ -112,6 +112,17 @@ class FrameSoA(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in SOA_FIELDS + DISPLAY_FIELDS]
 
 
+class Paths(C.Structure):
+    """bhrt_paths: xyz [n][P] Vector3D, xyz32 [n][P][3] float, count [n] int32; 0 = not produced."""
+    _fields_ = [("xyz", C.c_void_p), ("xyz32", C.c_void_p), ("count", C.c_void_p)]
+
+
+PATHS_MAX_POSITIONS = 65536  # BHRT_PATHS_MAX_POSITIONS
+# the hit fields a path launch produces (no colour or display field)
+PATH_HIT_FIELDS = ("result", "steps", "hit_x", "hit_y", "hit_z", "distance", "time_dilation",
+                   "sky_x", "sky_y", "sky_z")
+
+
 class Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("iterations", C.c_uint64), ("stages_full", C.c_uint64),
                 ("stages_far", C.c_uint64), ("stages_kerr", C.c_uint64),

@@ -73,6 +73,13 @@ _PROTOS = {
     "bhrt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                          _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
                                          C.c_int, C.c_int, _P(abi.FrameSoA), C.c_void_p]),
+    "bhrt_trace_paths_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                          _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                          C.c_int, C.c_int, C.c_int, _P(abi.Paths),
+                                          _P(abi.FrameSoA), C.c_void_p]),
+    "bhrt_trace_paths": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
+                                   C.c_int, C.c_int, _P(abi.Paths), _P(abi.FrameSoA)]),
     "bhrt_shard_rows": (C.c_int, [C.c_int, _P(abi.Rows)]),
     "bhrt_get_stats": (C.c_int, [_P(abi.Stats), C.c_int]),
     "bhrt_device_count": (C.c_int, []),
@@ -248,6 +255,37 @@ def render_frame_ss(bh, dk, cfg, cam, width, height, method=abi.INTEGRATOR_RK4, 
     _check(load().bhrt_render_frame_ss(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
                                        method, flags, _ptr(ss), _ptr(as_), C.byref(soa)),
            "bhrt_render_frame_ss")
+    return arrays
+
+
+def trace_paths_device(rays_ptr, n, bh, dk, cfg, method, max_positions, every, paths, hits,
+                       stream):
+    """bhrt_trace_paths_device: the recorded paths of n device rays (AoS Ray[n] at rays_ptr) into
+    the device arrays of `paths` (abi.Paths) and, if not None, the hit fields of `hits`
+    (abi.FrameSoA), asynchronous on a hipStream_t (int handle or None)."""
+    _check(load().bhrt_trace_paths_device(rays_ptr, int(n), _ptr(bh), _ptr(dk), _ptr(cfg), method,
+                                          int(max_positions), int(every), _ptr(paths),
+                                          _ptr(hits), C.c_void_p(stream) if stream else None),
+           "bhrt_trace_paths_device")
+
+
+def trace_paths(rays, bh, dk, cfg, method=abi.INTEGRATOR_RK4, max_positions=1001, every=1,
+                f32=False, fill=np.nan):
+    """bhrt_trace_paths into host numpy arrays: rays is a numpy array of abi.RAY_DTYPE. Returns a
+    dict with `xyz` [n, max_positions, 3] (float32 with f32, else float64; elements beyond a
+    ray's count keep `fill`), `count` [n] and the hit fields (abi.PATH_HIT_FIELDS)."""
+    rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+    n = len(rays)
+    xyz = np.full((n, int(max_positions), 3), fill, dtype=np.float32 if f32 else np.float64)
+    count = np.zeros(n, dtype=np.int32)
+    paths = abi.Paths(xyz=None if f32 else xyz.ctypes.data, xyz32=xyz.ctypes.data if f32 else None,
+                      count=count.ctypes.data)
+    arrays, soa = abi.alloc_soa(n, abi.PATH_HIT_FIELDS)
+    _check(load().bhrt_trace_paths(rays.ctypes.data, n, _ptr(bh), _ptr(dk), _ptr(cfg), method,
+                                   int(max_positions), int(every), C.byref(paths), C.byref(soa)),
+           "bhrt_trace_paths")
+    arrays["xyz"] = xyz
+    arrays["count"] = count
     return arrays
 
 

@@ -877,15 +877,18 @@ static void fill_origin(bhrt_kparams* kp, const Vector3D* origin) {
                                    k->use_approx);
 }
 
-/* one timed trace-kernel launch on `stream` (the context's own if NULL) */
-static int launch(devctx_t* c, bhrt_kparams* kp, hipStream_t stream) {
+/* one timed kernel launch on `stream` (the context's own if NULL) with a control block of the
+ * ring: the trace kernel (fn NULL), or fn(kp, arg, stream, ev0, ev1) -- a launcher with
+ * bhrt_launch_trace's contract that another host file names (bhrt_hook_launch) */
+static int launch_fn(devctx_t* c, bhrt_kparams* kp, hipStream_t stream, bhrt_launch_fn fn,
+                     const void* arg) {
     if (kp->n <= 0) return 0;
     if (!stream) {
         if (ctx_streams(c)) return -1;
         stream = c->stream;
     }
     /* the redo list follows the initial-state table (one extra field of the allocation) */
-    kp->redo = (int*)(kp->init + (size_t)BHRT_INIT_FIELDS * (size_t)kp->n);
+    if (kp->init) kp->redo = (int*)(kp->init + (size_t)BHRT_INIT_FIELDS * (size_t)kp->n);
     if (c->npend == BHRT_RING &&
         harvest(c, 1, stream, env_int("BHRT_HARVEST_ALL", 0) ? BHRT_RING : BHRT_RING / 2) != 0)
         return -1;
@@ -909,17 +912,23 @@ static int launch(devctx_t* c, bhrt_kparams* kp, hipStream_t stream) {
     }
     pending_t* p = &c->pend[c->npend];
     p->slot = slot;
-    p->redo = !(kp->skip_redo && kp->no_evict);
-    p->untested = bhrt_trace_untested(kp);
+    p->redo = fn ? 0 : !(kp->skip_redo && kp->no_evict); /* (fn: no redo pass, and no evictions) */
+    p->untested = fn ? 0 : bhrt_trace_untested(kp);
     p->ev0 = c->evpool[2 * slot]; /* (per slot: a slot has one pending launch at most) */
     p->ev1 = c->evpool[2 * slot + 1];
-    int e = bhrt_launch_trace(kp, (void*)stream, (void*)p->ev0, (void*)p->ev1);
+    int e = fn ? fn(kp, arg, (void*)stream, (void*)p->ev0, (void*)p->ev1)
+               : bhrt_launch_trace(kp, (void*)stream, (void*)p->ev0, (void*)p->ev1);
     if (e != 0) {
-        set_err("trace kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        set_err("%s kernel launch failed: %s", fn ? "path" : "trace",
+                hipGetErrorString((hipError_t)e));
         return -1;
     }
     c->npend++;
     return 0;
+}
+
+static int launch(devctx_t* c, bhrt_kparams* kp, hipStream_t stream) {
+    return launch_fn(c, kp, stream, NULL, NULL);
 }
 
 static int current_device(void) {
@@ -2398,7 +2407,7 @@ RayTraceResult trace_pixel(int px, int py, int W, int H, const Vector3D* cam_pos
 }
 
 /* ======================================================================================= */
-/* what supersample.c builds on (bhrt_host.h): wrappers only, no behaviour of their own     */
+/* what supersample.c and paths.c build on (bhrt_host.h): wrappers only                     */
 /* ======================================================================================= */
 void* bhrt_hook_ctx(void) { return ctx_get(current_device()); }
 
@@ -2427,12 +2436,30 @@ int bhrt_hook_trace_dirs(const double* d_dirs, int n, const BlackHoleParams* bh,
     return trace_rays_device(NULL, d_dirs, n, bh, dk, cfg, method, flags, out, stream, origin);
 }
 
+int bhrt_hook_trace_rays(const Ray* d_rays, int n, const BlackHoleParams* bh,
+                         const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                         IntegrationMethod method, int flags, const bhrt_frame_soa* out,
+                         void* stream) {
+    return trace_rays_device(d_rays, NULL, n, bh, dk, cfg, method, flags, out, stream, NULL);
+}
+
 void bhrt_hook_fill_camera(bhrt_kparams* kp, const BlackHoleParams* bh,
                            const AccretionDiskParams* dk, const SimulationConfig* cfg,
                            IntegrationMethod method, int flags, const bhrt_camera* cam, int W,
                            int H) {
     fill_scene(kp, bh, dk, cfg, method, flags);
     fill_camera(kp, cam, W, H);
+}
+
+int bhrt_hook_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                    const SimulationConfig* cfg, IntegrationMethod method, int flags) {
+    if (check_scene(bh, cfg)) return -1;
+    return fill_scene(kp, bh, dk, cfg, method, flags);
+}
+
+int bhrt_hook_launch(void* ctx, bhrt_kparams* kp, void* stream, bhrt_launch_fn fn,
+                     const void* arg) {
+    return launch_fn((devctx_t*)ctx, kp, (hipStream_t)stream, fn, arg);
 }
 
 int bhrt_hook_colour_fused(int method, int has_disk, int spin) {

@@ -167,6 +167,26 @@ typedef struct {
 int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream);
 int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream);
 
+/* Batched photon paths (paths.c; geodesic.hip k_paths): the launch's bhrt_kparams carries the
+ * scene, the AoS rays, n and the control block (ctl[0]: the claim counter, ctl[1..5]: the
+ * statistics, as k_trace's; its hit outputs are not used); this block the path outputs. */
+#ifndef BHRT_PATHS_STAGED /* the default store form: 1 staged through LDS, 0 direct (the faster
+                             on both measured batches: C4 0.155 vs 0.186 ms per 4096 rays,
+                             profiles/paths/bench_paths.jsonl); BHRT_PATHS_STORE picks at run time */
+#define BHRT_PATHS_STAGED 0
+#endif
+enum { BHRT_PATHS_RING = 8 }; /* staged form: points a lane holds in LDS between flushes */
+typedef struct {
+    int max_positions, every;
+    int staged;           /* store form of this launch (both are always built) */
+    bhrt_paths out;       /* device arrays; NULL fields skipped */
+} bhrt_paths_k;
+
+/* geodesic.hip; asynchronous on `stream`, ev0/ev1 (hipEvent_t, may be NULL) recorded around the
+ * kernel; returns 0 or a hipError_t value */
+int bhrt_launch_paths(const bhrt_kparams* kp, const bhrt_paths_k* pk, void* stream, void* ev0,
+                      void* ev1);
+
 /* update_particles (particle_sim.c:505-566) constants, from the BlackHoleParams and
  * SimulationConfig of the call */
 typedef struct {

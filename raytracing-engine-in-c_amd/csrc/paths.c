@@ -1,0 +1,263 @@
+/*
+ * paths.c -- batched photon paths: the recorded polylines of n rays in one launch
+ * (bhrt_api.h bhrt_trace_paths_device / bhrt_trace_paths; geodesic.hip k_paths).
+ *
+ * The device form is one launch of k_paths on the caller's stream, timed and counted like a
+ * trace launch: it takes a control block of the context's ring through bhrt_hook_launch (the
+ * block's first word is the kernel's claim counter, zero at launch like the rest), so it needs no
+ * scratch of its own. Where the caller asks for the rays' hit records, a trace launch of the same
+ * rays follows it on the same stream (paths_launch). The host form uploads the rays, runs the
+ * same launches into the context's cached device buffer and copies back what was stored.
+ *
+ * A file of its own, reaching bhrt_api.c through the hooks of bhrt_host.h: bhrt_api.c stays
+ * linkable without the launcher below (tests/fakehip).
+ */
+#define _GNU_SOURCE
+#include <hip/hip_runtime_api.h>
+#include <limits.h>
+#include <stdlib.h>
+#include <string.h>
+
+#pragma GCC visibility push(default)
+#include "../../include/bhrt_api.h"
+#pragma GCC visibility pop
+#include "bhrt_host.h"
+#include "bhrt_kernel.h"
+
+#define HIP_TRY(call)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            bhrt_set_err("%s failed: %s", #call, hipGetErrorString(e_));                      \
+            return -1;                                                                        \
+        }                                                                                     \
+    } while (0)
+
+/* element sizes of the hit fields a path launch produces, in bhrt_frame_soa's order (result,
+ * steps, hit_x/y/z, distance, time_dilation, sky_x/y/z); 0: not produced */
+enum { PATHS_NFIELDS = 15 };
+static const size_t k_hit_fsize[PATHS_NFIELDS] = {4, 4, 8, 8, 8, 8, 8, 8, 8, 8, 0, 0, 0, 0, 0};
+_Static_assert(sizeof(bhrt_frame_soa) == PATHS_NFIELDS * sizeof(void*), "bhrt_frame_soa fields");
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+/* the arguments that need no device: 0, or -1 with the error set */
+static int paths_check(const Ray* rays, int n, const BlackHoleParams* bh,
+                       const SimulationConfig* cfg, int max_positions, int every,
+                       const bhrt_paths* paths, const bhrt_frame_soa* hits) {
+    if (n <= 0) {
+        bhrt_set_err("paths: n = %d rays (at least 1)", n);
+        return -1;
+    }
+    if (!rays || !bh || !cfg) {
+        bhrt_set_err("paths: rays, blackhole and config must not be NULL");
+        return -1;
+    }
+    if (max_positions < 1 || max_positions > BHRT_PATHS_MAX_POSITIONS) {
+        bhrt_set_err("paths: max_positions = %d (1..%d)", max_positions, BHRT_PATHS_MAX_POSITIONS);
+        return -1;
+    }
+    if (every < 1) {
+        bhrt_set_err("paths: every = %d (at least 1)", every);
+        return -1;
+    }
+    if (!paths || !(paths->xyz || paths->xyz32 || paths->count)) {
+        bhrt_set_err("paths: none of xyz, xyz32 and count is asked for");
+        return -1;
+    }
+    if ((long)n * max_positions > INT_MAX) {
+        bhrt_set_err("paths: %d rays of %d positions are more than %d points", n, max_positions,
+                     INT_MAX);
+        return -1;
+    }
+    if (hits) {
+        void* const* f = (void* const*)hits;
+        for (int i = 0; i < PATHS_NFIELDS; i++)
+            if (f[i] && !k_hit_fsize[i]) {
+                bhrt_set_err("paths: the hits carry no colour or display field (field %d is not "
+                             "NULL)", i);
+                return -1;
+            }
+    }
+    return 0;
+}
+
+/* the store form: BHRT_PATHS_STORE=direct|staged, else the build's default */
+static int paths_staged(void) {
+    const char* e = getenv("BHRT_PATHS_STORE");
+    if (e && strcmp(e, "direct") == 0) return 0;
+    if (e && strcmp(e, "staged") == 0) return 1;
+    return BHRT_PATHS_STAGED;
+}
+
+static int paths_fn(const bhrt_kparams* kp, const void* arg, void* stream, void* ev0, void* ev1) {
+    return bhrt_launch_paths(kp, (const bhrt_paths_k*)arg, stream, ev0, ev1);
+}
+
+/* the launch on `st` (not NULL) of context ctx; all pointers are device pointers */
+static int paths_launch(void* ctx, void* st, const Ray* d_rays, int n, const BlackHoleParams* bh,
+                        const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                        IntegrationMethod method, int max_positions, int every,
+                        const bhrt_paths* paths, const bhrt_frame_soa* hits) {
+    bhrt_kparams kp;
+    if (bhrt_hook_scene(&kp, bh, dk, cfg, method, 0)) return -1;
+    kp.src = BHRT_SRC_RAYS;
+    kp.rays = d_rays;
+    kp.n = n;
+    bhrt_paths_k pk;
+    memset(&pk, 0, sizeof pk);
+    pk.max_positions = max_positions;
+    pk.every = every;
+    pk.staged = paths_staged();
+    pk.out = *paths;
+    if (bhrt_hook_launch(ctx, &kp, st, paths_fn, &pk)) return -1;
+    /* The hit records are the trace kernel's own, from its own launch behind the path launch:
+     * "what bhrt_trace_rays_device writes", bit for bit. k_paths integrates with the single-ray
+     * kernel's instantiation, so that its points are that kernel's bits; the trace kernel's
+     * multi-iteration trips round a long ray's last bits differently (the end point of 17 of
+     * 1000 C2 rays by up to 1.5e-15 relative, profiles/paths/hits_bits.txt), and one
+     * integration cannot carry both. bhrt_stats counts the two launches. */
+    if (hits && bhrt_hook_trace_rays(d_rays, n, bh, dk, cfg, method, 0, hits, st)) return -1;
+    return 0;
+}
+
+int bhrt_trace_paths_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
+                            const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                            IntegrationMethod method, int max_positions, int every,
+                            const bhrt_paths* paths, const bhrt_frame_soa* hits, void* stream) {
+    if (paths_check(d_rays, n, bh, cfg, max_positions, every, paths, hits)) return -1;
+    void* ctx = bhrt_hook_ctx();
+    if (!ctx) return -1;
+    if (stream)
+        return paths_launch(ctx, stream, d_rays, n, bh, dk, cfg, method, max_positions, every,
+                            paths, hits);
+    void* own = bhrt_hook_ctx_stream(ctx); /* the kernel runs on libbhrt's own stream */
+    if (!own) return -1;
+    if (bhrt_hook_null_unordered())
+        return paths_launch(ctx, own, d_rays, n, bh, dk, cfg, method, max_positions, every, paths,
+                            hits);
+    /* NULL stream: after the caller's default-stream work, and before what it queues next */
+    if (bhrt_hook_null_fence(ctx, 0)) return -1;
+    const int rc = paths_launch(ctx, own, d_rays, n, bh, dk, cfg, method, max_positions, every,
+                                paths, hits);
+    return bhrt_hook_null_fence(ctx, 1) ? -1 : rc;
+}
+
+/* A copy call's fixed cost, as the bytes a transfer moves meanwhile (about 10 us at the rate of
+ * a copy into pageable memory); BHRT_PATHS_COPY_CALL_BYTES overrides it (tests, A/B). */
+static size_t copy_call_bytes(void) {
+    const char* e = getenv("BHRT_PATHS_COPY_CALL_BYTES");
+    return e ? (size_t)strtoull(e, NULL, 10) : (size_t)131072;
+}
+
+/* Rows of `elem`-byte points back to the caller, count[i] points of ray i and nothing beyond
+ * them. Decided by total bytes: the whole rectangle moves n * P * elem bytes in one call (into a
+ * host staging block, the stored points then copied row by row: the caller's tails must keep what
+ * they hold); the ragged form moves only sum(count) * elem bytes but in one call per ray, each
+ * costing copy_call_bytes() more. The rectangle is taken when it is no more than the ragged total.
+ * A batch whose every row is full is its rectangle: one copy straight into the caller's array. */
+static int rows_back(void* host, const void* dev, const int32_t* count, int n, size_t P,
+                     size_t elem) {
+    size_t total = 0;
+    for (int i = 0; i < n; i++) total += (size_t)count[i];
+    const size_t rect = (size_t)n * P * elem;
+    if (total == (size_t)n * P) {
+        HIP_TRY(hipMemcpy(host, dev, rect, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (rect <= total * elem + (size_t)n * copy_call_bytes()) {
+        char* stage = (char*)malloc(rect);
+        if (stage) {
+            if (hipMemcpy(stage, dev, rect, hipMemcpyDeviceToHost) != hipSuccess) {
+                free(stage);
+                bhrt_set_err("paths: readback failed: %s", hipGetErrorString(hipGetLastError()));
+                return -1;
+            }
+            for (int i = 0; i < n; i++)
+                memcpy((char*)host + (size_t)i * P * elem, stage + (size_t)i * P * elem,
+                       (size_t)count[i] * elem);
+            free(stage);
+            return 0;
+        }
+        /* (no memory for the staging block: the ragged form needs none) */
+    }
+    for (int i = 0; i < n; i++)
+        if (count[i] > 0)
+            HIP_TRY(hipMemcpy((char*)host + (size_t)i * P * elem,
+                              (const char*)dev + (size_t)i * P * elem, (size_t)count[i] * elem,
+                              hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
+                     const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                     IntegrationMethod method, int max_positions, int every,
+                     const bhrt_paths* paths, const bhrt_frame_soa* hits) {
+    if (paths_check(rays, n, bh, cfg, max_positions, every, paths, hits)) return -1;
+    void* ctx = bhrt_hook_ctx();
+    void* st = ctx ? bhrt_hook_ctx_stream(ctx) : NULL;
+    if (!st) return -1;
+    const size_t P = (size_t)max_positions, N = (size_t)n;
+    /* the context's cached buffer: rays, the counts (always: the readback goes by them), the
+     * point arrays asked for, the hit fields asked for */
+    void* const* hhost = (void* const*)hits;
+    size_t bytes = align256(N * sizeof(Ray)) + align256(N * sizeof(int32_t));
+    if (paths->xyz) bytes += align256(N * P * sizeof(Vector3D));
+    if (paths->xyz32) bytes += align256(N * P * 3 * sizeof(float));
+    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
+        if (hhost[i]) bytes += align256(k_hit_fsize[i] * N);
+    char* p = (char*)bhrt_hook_ss_buffer(ctx, bytes);
+    if (!p) return -1;
+    Ray* d_rays = (Ray*)p;
+    p += align256(N * sizeof(Ray));
+    bhrt_paths dev;
+    memset(&dev, 0, sizeof dev);
+    dev.count = (int32_t*)p;
+    p += align256(N * sizeof(int32_t));
+    if (paths->xyz) {
+        dev.xyz = (Vector3D*)p;
+        p += align256(N * P * sizeof(Vector3D));
+    }
+    if (paths->xyz32) {
+        dev.xyz32 = (float*)p;
+        p += align256(N * P * 3 * sizeof(float));
+    }
+    bhrt_frame_soa dhits;
+    memset(&dhits, 0, sizeof dhits);
+    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
+        if (hhost[i]) {
+            ((void**)&dhits)[i] = p;
+            p += align256(k_hit_fsize[i] * N);
+        }
+    HIP_TRY(hipMemcpyAsync(d_rays, rays, N * sizeof(Ray), hipMemcpyHostToDevice, (hipStream_t)st));
+    if (paths_launch(ctx, st, d_rays, n, bh, dk, cfg, method, max_positions, every, &dev,
+                     hits ? &dhits : NULL))
+        return -1;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)st));
+    /* plain synchronous copies: caller memory is never page-locked */
+    int32_t* count = paths->count;
+    int32_t* own_count = NULL;
+    if (!count && (paths->xyz || paths->xyz32)) {
+        count = own_count = (int32_t*)malloc(N * sizeof(int32_t));
+        if (!count) {
+            bhrt_set_err("paths: no memory for %d counts", n);
+            return -1;
+        }
+    }
+    int rc = 0;
+    if (hipMemcpy(count, dev.count, N * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        bhrt_set_err("paths: readback failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = -1;
+    }
+    if (rc == 0 && paths->xyz)
+        rc = rows_back(paths->xyz, dev.xyz, count, n, P, sizeof(Vector3D));
+    if (rc == 0 && paths->xyz32)
+        rc = rows_back(paths->xyz32, dev.xyz32, count, n, P, 3 * sizeof(float));
+    free(own_count);
+    if (rc) return -1;
+    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
+        if (hhost[i])
+            HIP_TRY(hipMemcpy(hhost[i], ((void**)&dhits)[i], k_hit_fsize[i] * N,
+                              hipMemcpyDeviceToHost));
+    return 0;
+}

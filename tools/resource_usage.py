@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""VGPR / SGPR / scratch / occupancy of every k_trace instantiation (hipcc resource remarks).
+"""VGPR / SGPR / scratch / occupancy of every k_trace and k_paths instantiation (hipcc resource
+remarks); k_paths<METHOD, DISK, SPIN0, STAGED> with its LDS size.
 
 usage: python tools/resource_usage.py [extra hipcc -D flags]
 Template arguments are printed as METHOD DISK SPIN0 FAR HUGE INL [ACC]."""
@@ -20,6 +21,12 @@ for l in out.splitlines():
     if m and cur:
         rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
+    m = re.search(r"k_pathsILi(\d)ELb(\d)ELb(\d)ELb(\d)E", k)  # METHOD DISK SPIN0 STAGED
+    if m:
+        print("k_paths<%s>" % ",".join(m.groups()), "VGPR", v.get("VGPRs"), "SGPR", v.get("TotalSGPRs"),
+              "scratch", v.get("ScratchSize [bytes/lane]"), "waves", v.get("Occupancy [waves/SIMD]"),
+              "LDS", v.get("LDS Size [bytes/block]"))
+        continue
     m = re.search(r"k_traceILi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)EL[bi](\d)E(?:Lb(\d)E)?", k)
     if not m:
         continue
