@@ -1,5 +1,5 @@
 /*
- * bhrt_kernel.h -- launch parameters shared by the C host layer (bhrt_api.c) and the HIP
+ * bhrt_kernel.h -- launch parameters shared by the C host layer (bhrt_host.h) and the HIP
  * kernels (geodesic.hip). Plain C, passed by value as the kernel argument block, so every
  * field is wave-uniform and read through the scalar unit.
  *
@@ -43,7 +43,7 @@ typedef struct {
     int flags;   /* BHRT_FLAG_* */
     int spin0;   /* blackhole->spin == 0.0 */
     int far_bounded; /* a state within 2^40 stays below 2^400 over max_steps steps, far-field
-                        branch included (bhrt_api.c far_bounded; geodesic.hip repair_at_refill) */
+                        branch included (scene.c far_bounded; geodesic.hip repair_at_refill) */
     double rot_vmax; /* zero-acceleration paths: a ray with |state[5]| below this turns state[2]
                         by less than pi/4 per step for every step size (geodesic.hip
                         rotation_trig); a ray at or above it is re-traced by the redo pass */
@@ -109,7 +109,7 @@ typedef struct {
     bhrt_frame_soa out;   /* device SoA outputs; NULL fields skipped          */
     unsigned long long* ctl; /* [1..5] counters, [6] redo count, [7] redo queue head; the
                                 launch's slot of the control ring, zero at launch (the ring is
-                                filled with zeros on the GPU after each harvest, bhrt_api.c
+                                filled with zeros on the GPU after each harvest, context.c
                                 ring_order) */
     unsigned long long* qhead; /* ray-queue heads, queue q at qhead[q * queue_stride]; same slot */
     int queue_bits;       /* 2^queue_bits ray queues (<= BHRT_MAX_QUEUE_BITS)            */
@@ -123,7 +123,7 @@ typedef struct {
     int skip_redo;        /* the redo launch may be left out where no ray can be evicted
                              (geodesic.hip launch_trace_pair); BHRT_SKIP_REDO=0: always launch */
     int no_evict;         /* the host proved that no ray of this launch can be handed to the
-                             redo pass (bhrt_api.c origin_no_evict; camera frames and ray
+                             redo pass (scene.c origin_no_evict; camera frames and ray
                              arrays with one shared origin) */
     int block_lanes;      /* lanes per workgroup of the hot trace launch (64, 128 or 256) */
     int rays_shared;      /* BHRT_SRC_RAYS whose every origin is cam.pos (the host checked):

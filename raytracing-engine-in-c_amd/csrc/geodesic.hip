@@ -382,7 +382,7 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
 // The far-field branch's acceleration y5 * 2M / y0^2 is unclamped, but it only runs where
 // y0 > 15 rs, so its factor is below C = 2M / (15 rs)^2: per step the velocities grow by at
 // most a factor 1 + 2 h W C (plus 20 h W), W the step's largest weight sum. The host proves
-// from the scene (far_bounded, bhrt_api.c) that a state starting within 2^40 stays below 2^400
+// from the scene (far_bounded, scene.c) that a state starting within 2^40 stays below 2^400
 // for max_steps steps; far-field instantiations then drop the checks too, and a ray whose
 // initial state exceeds 2^40 -- or every ray of a launch the host could not prove bounded --
 // is handed to the HUGE redo pass (k_trace's refill), which keeps both checks every iteration.
@@ -543,7 +543,7 @@ __device__ __forceinline__ bool rkf45_accept(const double (&err)[6], const doubl
 // + 2u (1 + 3u) < 50u < 6e-15 for every component (v = 0: s4 = s5 = 0 and err = 0 exactly;
 // tiny v: the absolute rounding is below 2^-1074 against scale >= 1e-10), whatever the state:
 // every attempt passes the accept test -- RN(max err / scale) / tol <= 1 -- for any
-// tol >= 2^-30 (the host's condition, bhrt_api.c fill_scene: accept_all, with finite step
+// tol >= 2^-30 (the host's condition, scene.c bhrt_fill_scene: accept_all, with finite step
 // sizes and tol <= 2^300). The attempt is then y <- y5 alone: no y4, error, scale or test, and no
 // fixed point (C5: ~20 of ~87 VALU per attempt). The state is finite there (repair_at_refill),
 // so y + h s5 is too. The redo pass (HUGE) keeps the literal test.
@@ -876,7 +876,7 @@ __device__ __forceinline__ void ray_init_shared(Ray_& R, const bhrt_camera_k& cm
 // straight-line: every lane forms t, the candidate point and the radial test, and the four
 // rejections are ONE mask (a per-test early return became nested exec-mask regions, ~50 SALU
 // per iteration). The radial test compares s = qx^2 + qy^2 against the host's thresholds
-// instead of taking sqrt(s) (bhrt_api.c sqrt_lower/upper_bound). t = num * RN(1/den) for
+// instead of taking sqrt(s) (scene.c sqrt_lower/upper_bound). t = num * RN(1/den) for
 // |den| in [1e-10, 1e150) (a lane whose |den| < 1e-10 is rejected whatever its t); the IEEE
 // quotient, in a rare branch, otherwise (NaN den included). A t < 0 by signs (|num| > 0) is
 // negative here too, so the reference's rejection order is kept without a sign test.
@@ -1820,7 +1820,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                 kp.redo[atomicAdd(kp.ctl + 6, 1ull)] = rid;
                 // no redo pass follows a launch the host proved eviction-free: if that proof
                 // was wrong for this scene, the ray is marked, never left stale (the host's
-                // harvest reports the count as an error, bhrt_api.c)
+                // harvest reports the count as an error, context.c)
                 if (kc.no_evict && kc.skip_redo && kc.out.result) kc.out.result[rid] = RAY_ERROR;
                 live = false;
             } else if (term != T_NONE) {
@@ -2265,7 +2265,7 @@ void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
     bhrt_kparams k = kp;
     k.claim_shift = claim_shift(blocks, kp.claim_div, kp.queue_bits, lanes);
     k_trace<METHOD, DISK, SPIN0, FAR, false, INL, ACC><<<blocks, lanes, 0, st>>>(k);
-    // A launch the host proved eviction-free (bhrt_api.c origin_no_evict: every ray starts at
+    // A launch the host proved eviction-free (scene.c origin_no_evict: every ray starts at
     // one origin, and every state the loop can reach keeps its sincos arguments below 2^20 --
     // C1, C2, C3 -- or, on the zero-acceleration paths, C4 and C5, the loop has no sincos and
     // the one refill-time test |state[5]| < rot_vmax holds for every unit direction) hands no

@@ -10,17 +10,12 @@
  * BH_ERROR_SIMULATION) and bhrt_last_error() says why.
  */
 #define _GNU_SOURCE
-#include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
-#pragma GCC visibility push(default)
-#include "../../include/bhrt_api.h"
-#pragma GCC visibility pop
 #include "bhrt_host.h"
-#include "bhrt_kernel.h"
 
 #define PS_PI 3.14159265358979323846 /* particle_sim.c:15 */
 
@@ -293,15 +288,6 @@ static pctx_t* pctx_get(void) {
     return c;
 }
 
-#define PHIP(call)                                                                            \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            bhrt_set_err("%s failed: %s", #call, hipGetErrorString(e_));                      \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
-
 int bhrt_update_particles_steps(ParticleSystem* system, const BlackHoleParams* bh,
                                 const SimulationConfig* config, int steps, double* kernel_ms) {
     if (system == NULL || bh == NULL || config == NULL || steps < 0) {
@@ -318,7 +304,7 @@ int bhrt_update_particles_steps(ParticleSystem* system, const BlackHoleParams* b
         if (c->d_buf) (void)hipFree(c->d_buf);
         c->d_buf = NULL;
         c->cap = 0;
-        PHIP(hipMalloc((void**)&c->d_buf, bytes + bytes / 4));
+        HIP_TRY(hipMalloc((void**)&c->d_buf, bytes + bytes / 4));
         c->cap = bytes + bytes / 4;
     }
     bhrt_particle_k k;
@@ -328,18 +314,18 @@ int bhrt_update_particles_steps(ParticleSystem* system, const BlackHoleParams* b
     k.r_plus = bh->r_plus;
     k.dt = config->time_step;
     k.spin0 = bh->spin == 0.0;
-    PHIP(hipMemcpyAsync(c->d_buf, system->particles, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_buf, system->particles, bytes, hipMemcpyHostToDevice, c->stream));
     const int e = bhrt_launch_particles(c->d_buf, n, &k, steps, (void*)c->stream, (void*)c->ev0,
                                         (void*)c->ev1);
     if (e != 0) {
         bhrt_set_err("particle kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         return -1;
     }
-    PHIP(hipMemcpyAsync(system->particles, c->d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
-    PHIP(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(system->particles, c->d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (kernel_ms) {
         float ms = 0.f;
-        PHIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         *kernel_ms = ms;
     }
     return 0;

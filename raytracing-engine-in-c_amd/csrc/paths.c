@@ -3,43 +3,25 @@
  * (bhrt_api.h bhrt_trace_paths_device / bhrt_trace_paths; geodesic.hip k_paths).
  *
  * The device form is one launch of k_paths on the caller's stream, timed and counted like a
- * trace launch: it takes a control block of the context's ring through bhrt_hook_launch (the
+ * trace launch: it takes a control block of the context's ring through bhrt_ctx_launch_fn (the
  * block's first word is the kernel's claim counter, zero at launch like the rest), so it needs no
  * scratch of its own. Where the caller asks for the rays' hit records, a trace launch of the same
  * rays follows it on the same stream (paths_launch). The host form uploads the rays, runs the
  * same launches into the context's cached device buffer and copies back what was stored.
  *
- * A file of its own, reaching bhrt_api.c through the hooks of bhrt_host.h: bhrt_api.c stays
- * linkable without the launcher below (tests/fakehip).
+ * A file of its own (the Makefile's HOST_FEATURE): the files of HOST_CORE stay linkable without
+ * the launcher named below (tests/fakehip).
  */
 #define _GNU_SOURCE
-#include <hip/hip_runtime_api.h>
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 
-#pragma GCC visibility push(default)
-#include "../../include/bhrt_api.h"
-#pragma GCC visibility pop
 #include "bhrt_host.h"
-#include "bhrt_kernel.h"
 
-#define HIP_TRY(call)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            bhrt_set_err("%s failed: %s", #call, hipGetErrorString(e_));                      \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
-
-/* element sizes of the hit fields a path launch produces, in bhrt_frame_soa's order (result,
- * steps, hit_x/y/z, distance, time_dilation, sky_x/y/z); 0: not produced */
-enum { PATHS_NFIELDS = 15 };
-static const size_t k_hit_fsize[PATHS_NFIELDS] = {4, 4, 8, 8, 8, 8, 8, 8, 8, 8, 0, 0, 0, 0, 0};
-_Static_assert(sizeof(bhrt_frame_soa) == PATHS_NFIELDS * sizeof(void*), "bhrt_frame_soa fields");
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+/* the hit fields a path launch produces, as bits in bhrt_frame_soa's order: result, steps,
+ * hit_x/y/z, distance, time_dilation, sky_x/y/z (0..9) */
+#define HIT_FIELDS 0x3ffu
 
 /* the arguments that need no device: 0, or -1 with the error set */
 static int paths_check(const Ray* rays, int n, const BlackHoleParams* bh,
@@ -72,8 +54,8 @@ static int paths_check(const Ray* rays, int n, const BlackHoleParams* bh,
     }
     if (hits) {
         void* const* f = (void* const*)hits;
-        for (int i = 0; i < PATHS_NFIELDS; i++)
-            if (f[i] && !k_hit_fsize[i]) {
+        for (int i = 0; i < BHRT_NFIELDS; i++)
+            if (f[i] && !(HIT_FIELDS >> i & 1u)) {
                 bhrt_set_err("paths: the hits carry no colour or display field (field %d is not "
                              "NULL)", i);
                 return -1;
@@ -94,13 +76,14 @@ static int paths_fn(const bhrt_kparams* kp, const void* arg, void* stream, void*
     return bhrt_launch_paths(kp, (const bhrt_paths_k*)arg, stream, ev0, ev1);
 }
 
-/* the launch on `st` (not NULL) of context ctx; all pointers are device pointers */
-static int paths_launch(void* ctx, void* st, const Ray* d_rays, int n, const BlackHoleParams* bh,
-                        const AccretionDiskParams* dk, const SimulationConfig* cfg,
+/* the launch on `st` (not NULL) of context c; all pointers are device pointers */
+static int paths_launch(devctx_t* c, hipStream_t st, const Ray* d_rays, int n,
+                        const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                        const SimulationConfig* cfg,
                         IntegrationMethod method, int max_positions, int every,
                         const bhrt_paths* paths, const bhrt_frame_soa* hits) {
     bhrt_kparams kp;
-    if (bhrt_hook_scene(&kp, bh, dk, cfg, method, 0)) return -1;
+    if (bhrt_check_scene(bh, cfg) || bhrt_fill_scene(&kp, bh, dk, cfg, method, 0)) return -1;
     kp.src = BHRT_SRC_RAYS;
     kp.rays = d_rays;
     kp.n = n;
@@ -110,15 +93,34 @@ static int paths_launch(void* ctx, void* st, const Ray* d_rays, int n, const Bla
     pk.every = every;
     pk.staged = paths_staged();
     pk.out = *paths;
-    if (bhrt_hook_launch(ctx, &kp, st, paths_fn, &pk)) return -1;
+    if (bhrt_ctx_launch_fn(c, &kp, st, paths_fn, &pk)) return -1;
     /* The hit records are the trace kernel's own, from its own launch behind the path launch:
      * "what bhrt_trace_rays_device writes", bit for bit. k_paths integrates with the single-ray
      * kernel's instantiation, so that its points are that kernel's bits; the trace kernel's
      * multi-iteration trips round a long ray's last bits differently (the end point of 17 of
      * 1000 C2 rays by up to 1.5e-15 relative, profiles/paths/hits_bits.txt), and one
      * integration cannot carry both. bhrt_stats counts the two launches. */
-    if (hits && bhrt_hook_trace_rays(d_rays, n, bh, dk, cfg, method, 0, hits, st)) return -1;
+    if (hits && bhrt_rays_on_device(d_rays, NULL, n, bh, dk, cfg, method, 0, hits, st, NULL))
+        return -1;
     return 0;
+}
+
+typedef struct { /* paths_launch's arguments, for its run under the stream rule */
+    const Ray* d_rays;
+    int n;
+    const BlackHoleParams* bh;
+    const AccretionDiskParams* dk;
+    const SimulationConfig* cfg;
+    IntegrationMethod method;
+    int max_positions, every;
+    const bhrt_paths* paths;
+    const bhrt_frame_soa* hits;
+} paths_call;
+
+static int paths_body(devctx_t* c, hipStream_t st, const void* arg) {
+    const paths_call* a = (const paths_call*)arg;
+    return paths_launch(c, st, a->d_rays, a->n, a->bh, a->dk, a->cfg, a->method, a->max_positions,
+                        a->every, a->paths, a->hits);
 }
 
 int bhrt_trace_paths_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
@@ -126,21 +128,12 @@ int bhrt_trace_paths_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
                             IntegrationMethod method, int max_positions, int every,
                             const bhrt_paths* paths, const bhrt_frame_soa* hits, void* stream) {
     if (paths_check(d_rays, n, bh, cfg, max_positions, every, paths, hits)) return -1;
-    void* ctx = bhrt_hook_ctx();
-    if (!ctx) return -1;
-    if (stream)
-        return paths_launch(ctx, stream, d_rays, n, bh, dk, cfg, method, max_positions, every,
-                            paths, hits);
-    void* own = bhrt_hook_ctx_stream(ctx); /* the kernel runs on libbhrt's own stream */
-    if (!own) return -1;
-    if (bhrt_hook_null_unordered())
-        return paths_launch(ctx, own, d_rays, n, bh, dk, cfg, method, max_positions, every, paths,
-                            hits);
-    /* NULL stream: after the caller's default-stream work, and before what it queues next */
-    if (bhrt_hook_null_fence(ctx, 0)) return -1;
-    const int rc = paths_launch(ctx, own, d_rays, n, bh, dk, cfg, method, max_positions, every,
-                                paths, hits);
-    return bhrt_hook_null_fence(ctx, 1) ? -1 : rc;
+    devctx_t* c = bhrt_ctx_get(bhrt_current_device());
+    if (!c) return -1;
+    /* NULL stream: the kernel runs on libbhrt's own stream, after the caller's default-stream
+     * work and before what it queues next */
+    const paths_call a = {d_rays, n, bh, dk, cfg, method, max_positions, every, paths, hits};
+    return bhrt_on_stream(c, (hipStream_t)stream, paths_body, &a);
 }
 
 /* A copy call's fixed cost, as the bytes a transfer moves meanwhile (about 10 us at the rate of
@@ -194,9 +187,9 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
                      IntegrationMethod method, int max_positions, int every,
                      const bhrt_paths* paths, const bhrt_frame_soa* hits) {
     if (paths_check(rays, n, bh, cfg, max_positions, every, paths, hits)) return -1;
-    void* ctx = bhrt_hook_ctx();
-    void* st = ctx ? bhrt_hook_ctx_stream(ctx) : NULL;
-    if (!st) return -1;
+    devctx_t* c = bhrt_ctx_get(bhrt_current_device());
+    if (!c || bhrt_ctx_streams(c)) return -1;
+    hipStream_t st = c->stream;
     const size_t P = (size_t)max_positions, N = (size_t)n;
     /* the context's cached buffer: rays, the counts (always: the readback goes by them), the
      * point arrays asked for, the hit fields asked for */
@@ -204,10 +197,9 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
     size_t bytes = align256(N * sizeof(Ray)) + align256(N * sizeof(int32_t));
     if (paths->xyz) bytes += align256(N * P * sizeof(Vector3D));
     if (paths->xyz32) bytes += align256(N * P * 3 * sizeof(float));
-    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
-        if (hhost[i]) bytes += align256(k_hit_fsize[i] * N);
-    char* p = (char*)bhrt_hook_ss_buffer(ctx, bytes);
-    if (!p) return -1;
+    if (hits) bytes += bhrt_soa_bytes(hits, n);
+    if (bhrt_ensure(&c->d_ss, &c->cap_ss, bytes ? bytes : 256, 0)) return -1;
+    char* p = (char*)c->d_ss;
     Ray* d_rays = (Ray*)p;
     p += align256(N * sizeof(Ray));
     bhrt_paths dev;
@@ -222,18 +214,13 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
         dev.xyz32 = (float*)p;
         p += align256(N * P * 3 * sizeof(float));
     }
-    bhrt_frame_soa dhits;
-    memset(&dhits, 0, sizeof dhits);
-    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
-        if (hhost[i]) {
-            ((void**)&dhits)[i] = p;
-            p += align256(k_hit_fsize[i] * N);
-        }
-    HIP_TRY(hipMemcpyAsync(d_rays, rays, N * sizeof(Ray), hipMemcpyHostToDevice, (hipStream_t)st));
-    if (paths_launch(ctx, st, d_rays, n, bh, dk, cfg, method, max_positions, every, &dev,
+    bhrt_frame_soa dhits; /* (paths_check: only fields a path launch produces) */
+    if (hits) bhrt_soa_carve(&p, hits, n, &dhits);
+    HIP_TRY(hipMemcpyAsync(d_rays, rays, N * sizeof(Ray), hipMemcpyHostToDevice, st));
+    if (paths_launch(c, st, d_rays, n, bh, dk, cfg, method, max_positions, every, &dev,
                      hits ? &dhits : NULL))
         return -1;
-    HIP_TRY(hipStreamSynchronize((hipStream_t)st));
+    HIP_TRY(hipStreamSynchronize(st));
     /* plain synchronous copies: caller memory is never page-locked */
     int32_t* count = paths->count;
     int32_t* own_count = NULL;
@@ -255,9 +242,9 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
         rc = rows_back(paths->xyz32, dev.xyz32, count, n, P, 3 * sizeof(float));
     free(own_count);
     if (rc) return -1;
-    for (int i = 0; hits && i < PATHS_NFIELDS; i++)
+    for (int i = 0; hits && i < BHRT_NFIELDS; i++)
         if (hhost[i])
-            HIP_TRY(hipMemcpy(hhost[i], ((void**)&dhits)[i], k_hit_fsize[i] * N,
+            HIP_TRY(hipMemcpy(hhost[i], ((void**)&dhits)[i], k_fsize[i] * N,
                               hipMemcpyDeviceToHost));
     return 0;
 }

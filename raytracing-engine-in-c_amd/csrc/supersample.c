@@ -8,36 +8,22 @@
  *                 launches, each with its sample's offset in the argument block's camera;
  *   the trace     ONE launch of n * S rays with a shared origin and packed directions -- the
  *                 path trace_rays_batch takes for rays of one origin (bhrt_api.c
- *                 trace_rays_device) -- writing each sample's class and colour;
+ *                 bhrt_rays_on_device) -- writing each sample's class and colour;
  *   k_ss_resolve  per pixel, the S colours added in sample order from 0.0 and divided by S, the
  *                 display conversions, and sample 0's class.
  * The sample scratch (24 B of directions, 24 B of colour, 4 B of class per sample ray; 16 B of
  * hit point more where BHRT_FUSE_COLOUR=0 takes the separate colour pass) lies behind the
- * launch's own 176 B per ray in the SAME per-stream allocation (bhrt_api.c stream_scratch), so
- * frames on two streams never share it and it stays valid until the stream's resolve has run.
+ * launch's own 176 B per ray in the SAME per-stream allocation (context.c bhrt_stream_scratch),
+ * so frames on two streams never share it and it stays valid until the stream's resolve has run.
  *
- * A file of its own, reaching bhrt_api.c through the hooks of bhrt_host.h: bhrt_api.c stays
- * linkable without the two launchers below (tests/fakehip).
+ * A file of its own (the Makefile's HOST_FEATURE): the files of HOST_CORE stay linkable without
+ * the two launchers named below (tests/fakehip).
  */
 #define _GNU_SOURCE
-#include <hip/hip_runtime_api.h>
 #include <limits.h>
 #include <string.h>
 
-#pragma GCC visibility push(default)
-#include "../../include/bhrt_api.h"
-#pragma GCC visibility pop
 #include "bhrt_host.h"
-#include "bhrt_kernel.h"
-
-#define HIP_TRY(call)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            bhrt_set_err("%s failed: %s", #call, hipGetErrorString(e_));                      \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
 
 int bhrt_sample_offsets(const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
                         double* offset_x, double* offset_y, int capacity) {
@@ -65,19 +51,15 @@ int bhrt_sample_offsets(const SupersamplingParams* ss, const AdaptiveSamplingPar
     for (int s = 0; s < samples; s++) {
         offset_x[s] = offset_y[s] = 0.5;
         if (jittered)
-            bhrt_hook_jitter(s, ss->samples_per_pixel, ss->jitter_method, ss->jitter_strength,
-                             &offset_x[s], &offset_y[s]);
+            bhrt_jitter(s, ss->samples_per_pixel, ss->jitter_method, ss->jitter_strength,
+                        &offset_x[s], &offset_y[s]);
     }
     return samples;
 }
 
-/* element sizes of the fields a supersampled frame can produce, in bhrt_frame_soa's order
- * (result, rgb_r/g/b, rgba32f, rgba8); 0: not produced */
-enum { SS_NFIELDS = 15 };
-static const size_t k_ss_fsize[SS_NFIELDS] = {4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 8, 8, 8, 16, 4};
-_Static_assert(sizeof(bhrt_frame_soa) == SS_NFIELDS * sizeof(void*), "bhrt_frame_soa fields");
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+/* the fields a supersampled frame can produce, as bits in bhrt_frame_soa's order: result (0),
+ * rgb_r/g/b (10..12), rgba32f (13), rgba8 (14) */
+#define SS_FIELDS 0x7c01u
 
 typedef struct { /* a checked frame: shard pixels, samples per pixel and their offsets */
     int n, samples;
@@ -104,8 +86,8 @@ static int ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, cons
         return -1;
     }
     void* const* f = (void* const*)out;
-    for (int i = 0; i < SS_NFIELDS; i++)
-        if (f[i] && !k_ss_fsize[i]) {
+    for (int i = 0; i < BHRT_NFIELDS; i++)
+        if (f[i] && !(SS_FIELDS >> i & 1u)) {
             bhrt_set_err("supersampled frame: only result, rgb_r/g/b, rgba32f and rgba8 are "
                          "produced (field %d is not NULL)", i);
             return -1;
@@ -126,21 +108,22 @@ static int ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, cons
     return 0;
 }
 
-/* the frame on `st` (not NULL) of context ctx */
-static int ss_frame(void* ctx, void* st, const BlackHoleParams* bh, const AccretionDiskParams* dk,
-                    const SimulationConfig* cfg, const bhrt_camera* cam, int W, int H,
-                    const bhrt_rows* rows, IntegrationMethod method, int flags,
-                    const ss_plan* k, const bhrt_frame_soa* out) {
+/* the frame on `st` (not NULL) of context c */
+static int ss_frame(devctx_t* c, hipStream_t st, const BlackHoleParams* bh,
+                    const AccretionDiskParams* dk, const SimulationConfig* cfg,
+                    const bhrt_camera* cam, int W, int H, const bhrt_rows* rows,
+                    IntegrationMethod method, int flags, const ss_plan* k,
+                    const bhrt_frame_soa* out) {
     const int n = k->n;
     if (n == 0) return 0;
     const size_t N = (size_t)n * (size_t)k->samples;
-    const int fused = bhrt_hook_colour_fused((int)method, dk != NULL, bh->spin != 0.0);
-    /* the trace launch's own scratch first (what trace_rays_device asks for), then ours */
+    const int fused = bhrt_colour_fused((int)method, dk != NULL, bh->spin != 0.0);
+    /* the trace launch's own scratch first (what bhrt_rays_on_device asks for), then ours */
     const size_t launch_bytes = align256((size_t)(BHRT_INIT_FIELDS + 1) * sizeof(double) * N);
     const size_t plane8 = align256(8 * N), plane4 = align256(4 * N);
     const size_t bytes = launch_bytes + align256(24 * N) + 3 * plane8 + plane4 +
                          (fused ? 0 : 2 * plane8);
-    char* p = (char*)bhrt_hook_scratch(ctx, st, bytes);
+    char* p = (char*)bhrt_stream_scratch(c, st, bytes);
     if (!p) return -1;
     p += launch_bytes;
     bhrt_frame_soa smp; /* the sample planes the trace writes */
@@ -158,8 +141,9 @@ static int ss_frame(void* ctx, void* st, const BlackHoleParams* bh, const Accret
         smp.hit_y = (double*)(p + plane8);
     }
     bhrt_kparams kp;
-    bhrt_hook_fill_camera(&kp, bh, dk, cfg, method, flags, cam, W, H);
-    if (rows && rows->num_shards > 1) { /* (as render_frame_device sets a shard up) */
+    bhrt_fill_scene(&kp, bh, dk, cfg, method, flags);
+    bhrt_fill_camera(&kp, cam, W, H);
+    if (rows && rows->num_shards > 1) { /* (as bhrt_frame_on_device sets a shard up) */
         kp.cam.rows = *rows;
         kp.cam.inv_block = 1.0 / (double)rows->row_block;
     }
@@ -179,8 +163,8 @@ static int ss_frame(void* ctx, void* st, const BlackHoleParams* bh, const Accret
         bhrt_set_err("sample ray kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         return -1;
     }
-    if (bhrt_hook_trace_dirs(dirs, (int)N, bh, dk, cfg, method, flags, &smp, st,
-                             &cam->position))
+    if (bhrt_rays_on_device(NULL, dirs, (int)N, bh, dk, cfg, method, flags, &smp, st,
+                            &cam->position))
         return -1;
     bhrt_ss_resolve_k r;
     memset(&r, 0, sizeof r);
@@ -200,6 +184,25 @@ static int ss_frame(void* ctx, void* st, const BlackHoleParams* bh, const Accret
     return 0;
 }
 
+typedef struct { /* ss_frame's arguments, for its run under the stream rule */
+    const BlackHoleParams* bh;
+    const AccretionDiskParams* dk;
+    const SimulationConfig* cfg;
+    const bhrt_camera* cam;
+    int W, H;
+    const bhrt_rows* rows;
+    IntegrationMethod method;
+    int flags;
+    const ss_plan* k;
+    const bhrt_frame_soa* out;
+} ss_call;
+
+static int ss_body(devctx_t* c, hipStream_t st, const void* arg) {
+    const ss_call* a = (const ss_call*)arg;
+    return ss_frame(c, st, a->bh, a->dk, a->cfg, a->cam, a->W, a->H, a->rows, a->method, a->flags,
+                    a->k, a->out);
+}
+
 int bhrt_render_frame_ss_device(const BlackHoleParams* bh, const AccretionDiskParams* dk,
                                 const SimulationConfig* cfg, const bhrt_camera* cam, int W, int H,
                                 const bhrt_rows* rows, IntegrationMethod method, int flags,
@@ -207,18 +210,12 @@ int bhrt_render_frame_ss_device(const BlackHoleParams* bh, const AccretionDiskPa
                                 const bhrt_frame_soa* out, void* stream) {
     ss_plan k;
     if (ss_check(bh, cfg, cam, W, H, rows, ss, as, out, &k)) return -1;
-    void* ctx = bhrt_hook_ctx();
-    if (!ctx) return -1;
-    if (stream)
-        return ss_frame(ctx, stream, bh, dk, cfg, cam, W, H, rows, method, flags, &k, out);
-    void* own = bhrt_hook_ctx_stream(ctx); /* the kernels run on libbhrt's own stream */
-    if (!own) return -1;
-    if (bhrt_hook_null_unordered())
-        return ss_frame(ctx, own, bh, dk, cfg, cam, W, H, rows, method, flags, &k, out);
-    /* NULL stream: after the caller's default-stream work, and before what it queues next */
-    if (bhrt_hook_null_fence(ctx, 0)) return -1;
-    const int rc = ss_frame(ctx, own, bh, dk, cfg, cam, W, H, rows, method, flags, &k, out);
-    return bhrt_hook_null_fence(ctx, 1) ? -1 : rc;
+    devctx_t* c = bhrt_ctx_get(bhrt_current_device());
+    if (!c) return -1;
+    /* NULL stream: the kernels run on libbhrt's own stream, after the caller's default-stream
+     * work and before what it queues next */
+    const ss_call a = {bh, dk, cfg, cam, W, H, rows, method, flags, &k, out};
+    return bhrt_on_stream(c, (hipStream_t)stream, ss_body, &a);
 }
 
 int bhrt_render_frame_ss(const BlackHoleParams* bh, const AccretionDiskParams* dk,
@@ -228,29 +225,22 @@ int bhrt_render_frame_ss(const BlackHoleParams* bh, const AccretionDiskParams* d
     ss_plan k;
     if (ss_check(bh, cfg, cam, W, H, NULL, ss, as, out, &k)) return -1;
     const int n = k.n;
-    void* ctx = bhrt_hook_ctx();
-    void* st = ctx ? bhrt_hook_ctx_stream(ctx) : NULL;
-    if (!st) return -1;
-    /* device outputs for the caller's fields, from the context's cached buffer */
-    void* const* host = (void* const*)out;
-    size_t bytes = 0;
-    for (int i = 0; i < SS_NFIELDS; i++)
-        if (host[i]) bytes += align256(k_ss_fsize[i] * (size_t)n);
-    char* p = (char*)bhrt_hook_ss_buffer(ctx, bytes);
-    if (!p) return -1;
+    devctx_t* c = bhrt_ctx_get(bhrt_current_device());
+    if (!c || bhrt_ctx_streams(c)) return -1;
+    /* device outputs for the caller's fields (ss_check: all of them are fields a frame
+     * produces), from the context's cached buffer */
+    const size_t bytes = bhrt_soa_bytes(out, n);
+    if (bhrt_ensure(&c->d_ss, &c->cap_ss, bytes ? bytes : 256, 0)) return -1;
+    char* p = (char*)c->d_ss;
     bhrt_frame_soa dev;
-    memset(&dev, 0, sizeof dev);
-    for (int i = 0; i < SS_NFIELDS; i++)
-        if (host[i]) {
-            ((void**)&dev)[i] = p;
-            p += align256(k_ss_fsize[i] * (size_t)n);
-        }
-    if (ss_frame(ctx, st, bh, dk, cfg, cam, W, H, NULL, method, flags, &k, &dev)) return -1;
-    HIP_TRY(hipStreamSynchronize((hipStream_t)st));
+    bhrt_soa_carve(&p, out, n, &dev);
+    if (ss_frame(c, c->stream, bh, dk, cfg, cam, W, H, NULL, method, flags, &k, &dev)) return -1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
     /* plain synchronous copies: caller memory is never page-locked */
-    for (int i = 0; i < SS_NFIELDS; i++)
+    void* const* host = (void* const*)out;
+    for (int i = 0; i < BHRT_NFIELDS; i++)
         if (host[i])
-            HIP_TRY(hipMemcpy(host[i], ((void**)&dev)[i], k_ss_fsize[i] * (size_t)n,
+            HIP_TRY(hipMemcpy(host[i], ((void**)&dev)[i], k_fsize[i] * (size_t)n,
                               hipMemcpyDeviceToHost));
     return 0;
 }

@@ -1,7 +1,7 @@
 /* asan_driver.c -- host code under AddressSanitizer + UBSan.
  *
  * Built by tests/test_sanitizers.py with -fsanitize=address,undefined from: the oracle
- * (oracle/oracle.c), libbhrt's host C (bhrt_api.c, particles.c, kerr_helpers.c) and the
+ * (oracle/oracle.c), libbhrt's host C (the Makefile's HOST_CORE files) and the
  * stubs below for the three device launchers (geodesic.hip / particles.hip are device code,
  * not instrumented; without a GPU every device entry point must fail cleanly anyway). */
 #include <math.h>

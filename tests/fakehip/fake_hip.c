@@ -1,5 +1,5 @@
 /* fake_hip.c -- a host-memory stand-in for the HIP runtime calls libbhrt's host C makes, so
- * bhrt_api.c can be driven with SEVERAL simulated devices on a machine without a GPU, under
+ * it can be driven with SEVERAL simulated devices on a machine without a GPU, under
  * ASan/UBSan and TSan (tests/test_multidevice_host.py; VERDICT r1 "multi-device state").
  *
  * Device memory is malloc'ed and tagged with the device that allocated it; every stream

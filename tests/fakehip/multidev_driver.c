@@ -1,4 +1,4 @@
-/* multidev_driver.c -- libbhrt's host layer (bhrt_api.c) on SIMULATED devices (fake_hip.c):
+/* multidev_driver.c -- libbhrt's host layer (HOST_CORE) on SIMULATED devices (fake_hip.c):
  * frames split over two devices and several chunks, DMA'd or staged into caller arrays,
  * frames in flight (bhrt_render_frame_async), ray batches split over the devices and the
  * pipelined trace_rays_batch, all from two host threads at once. Built by
@@ -314,7 +314,7 @@ static void run(BlackHoleParams* bh, SimulationConfig* cfg, AccretionDiskParams*
     bhrt_stats st;
     CHECK(bhrt_get_stats(&st, 1) == 0 && st.launches > 0 && st.rays > 0, "stats");
     /* the control ring: 700 device frames over three streams with no wait between them. The
-     * launch that finds the ring full harvests its older half and reuses those slots (bhrt_api.c
+     * launch that finds the ring full harvests its older half and reuses those slots (context.c
      * harvest); the launcher above adds each launch's rays to its slot's counter, so a slot
      * reused without being zeroed, or a launch counted twice or never, shows in the total. */
     {

@@ -1,5 +1,5 @@
-/* paths_driver.c -- the host form of batched photon paths (paths.c bhrt_trace_paths, through
- * bhrt_api.c's hooks) on a SIMULATED device (fake_hip.c), built by tests/test_paths_cpu.py under
+/* paths_driver.c -- the host form of batched photon paths (paths.c bhrt_trace_paths, over
+ * the HOST_CORE files) on a SIMULATED device (fake_hip.c), built by tests/test_paths_cpu.py under
  * ASan+UBSan as a stand-alone program.
  *
  * The path launcher is a stub that checks every launch buffer against the simulated device and
@@ -127,7 +127,7 @@ int bhrt_launch_trace(const bhrt_kparams* kp, void* stream, void* ev0, void* ev1
     g_traces++;
     return 0;
 }
-/* the launchers bhrt_api.c and particles.c name besides; neither is reached here */
+/* the launchers dropin.c and particles.c name besides; neither is reached here */
 int bhrt_launch_path(const bhrt_kparams* kp, const double* o, const double* d, Vector3D* p,
                      int m, int* nn, int nin, void* st) {
     (void)kp; (void)o; (void)d; (void)p; (void)m; (void)nn; (void)nin; (void)st;

@@ -1,0 +1,24 @@
+"""The C host files of libbhrt as csrc/Makefile lists them, for the tests that compile them into
+stand-alone drivers (simulated devices, sanitizers) or read them: one list, the Makefile's."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
+
+
+def _listed(target):
+    out = subprocess.run(["make", "-s", "-C", CSRC, target], check=True, capture_output=True,
+                         text=True).stdout
+    return out.split()
+
+
+def host_core():
+    """HOST_CORE: the files every driver links, which name only the trace, path and particle
+    launchers (absolute paths)."""
+    return _listed("print-host-core")
+
+
+def host_feature():
+    """HOST_FEATURE: the files that name launchers of their own (absolute paths)."""
+    return _listed("print-host-feature")

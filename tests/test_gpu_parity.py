@@ -544,7 +544,7 @@ def test_large_argument_rays_take_the_redo_path(bhrt_lib, oracle):
 @pytest.mark.parametrize("method", [abi.INTEGRATOR_RK4, abi.INTEGRATOR_RKF45])
 def test_unbounded_far_field_launch_takes_the_redo_path(bhrt_lib, oracle, method):
     """geodesic.hip repair_at_refill: the far-field instantiations drop the per-iteration state
-    recovery (and RKF45's literal accept quotient) only where bhrt_api.c far_bounded proves that
+    recovery (and RKF45's literal accept quotient) only where scene.c far_bounded proves that
     no state can overflow. A tiny black hole (M = 1e-3: the far-field factor 2M / (15 rs)^2 is
     2.2, so h S C > 1/2) is not provable: every ray is handed to the HUGE redo pass, whose
     literal per-iteration checks must give the oracle's frame (camera B origin beyond 15 rs,
@@ -858,8 +858,8 @@ def test_full_frame_every_ray_vs_oracle(bhrt_lib, oracle, cname):
     n = W * (H if rows is None else bhrt_lib.shard_rows(H, rows))
     # The outputs are filled on torch's default stream (the legacy null stream) behind a busy
     # kernel, rendered with hip_stream NULL and read back on the default stream, with no host
-    # sync anywhere: NULL orders the frame after the fills and before the reads (null_fence,
-    # bhrt_api.c). Round 5 needed a torch.cuda.synchronize() on each side (a fill still queued
+    # sync anywhere: NULL orders the frame after the fills and before the reads (bhrt_null_fence,
+    # context.c). Round 5 needed a torch.cuda.synchronize() on each side (a fill still queued
     # behind the trace kernel overwrote 3.37 M rays of C5's frame).
     t = _default_stream_filled_outputs(torch, n)
     bhrt_lib.render_frame_device(bh, dk, cfg, cam, W, H, rows, c.method, c.flags,
@@ -1177,7 +1177,7 @@ def test_stage_counts_are_counted(bhrt_lib):
 @pytest.mark.parametrize("cname,camname,W,H", STAGE_CASES)
 def test_redo_pass_left_out_where_no_ray_can_need_it(bhrt_lib, monkeypatch, cname, camname, W,
                                                      H):
-    """bhrt_api.c origin_no_evict proves from the scene and the shared origin that no ray of a
+    """scene.c origin_no_evict proves from the scene and the shared origin that no ray of a
     camera frame can be handed to the redo pass, and the launcher then leaves that launch out
      -- on every BASELINE frame (camera B); the bound is conservative, so a
     scene it cannot prove (RKF45 from camera V's far origin) keeps the launch. With the launch
@@ -1218,7 +1218,7 @@ def test_redo_pass_left_out_where_no_ray_can_need_it(bhrt_lib, monkeypatch, cnam
 
 def test_control_ring_wraps(bhrt_lib):
     """600 device frames back to back on one stream, no sync between them: the launch that
-    finds the thread's control ring full (256 slots, bhrt_api.c BHRT_RING) harvests it and
+    finds the thread's control ring full (256 slots, bhrt_host.h BHRT_RING) harvests it and
     zeroes it, twice here. Every frame must be the first one bit for bit (a slot reused
     without its queue heads zeroed would skip rays) and the statistics must count every launch
     once; a discarding reset (bhrt_get_stats(NULL, 1)) drops pending launches unread."""
@@ -1268,7 +1268,7 @@ def test_control_ring_wraps(bhrt_lib):
 @pytest.mark.gpu
 def test_control_ring_wraps_across_streams(bhrt_lib):
     """The ring-full launch harvests the older half of the control ring only and reuses it
-    (bhrt_api.c harvest): 700 frames rotating over three caller streams, no sync between them,
+    (context.c harvest): 700 frames rotating over three caller streams, no sync between them,
     so the refilled half is zeroed on one stream while the newer half's frames still run on the
     others, and every stream's first launch after the fill waits for it. Every frame must equal
     the first bit for bit and the statistics must count every launch once."""

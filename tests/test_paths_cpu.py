@@ -16,6 +16,7 @@ import pytest
 
 from conftest import ROOT, golden
 from bhrt import abi, lib
+from host_sources import host_core
 
 CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
 FAKE = os.path.join(ROOT, "tests", "fakehip")
@@ -199,8 +200,8 @@ def test_symbols_exported():
 
 
 def test_host_files_of_the_simulated_device_build_do_not_name_the_launcher():
-    for f in ("bhrt_api.c", "particles.c", "kerr_helpers.c"):
-        assert "bhrt_launch_paths" not in open(os.path.join(CSRC, f)).read(), f
+    for f in host_core():
+        assert "bhrt_launch_paths" not in open(f).read(), f
     assert "bhrt_launch_paths" in open(os.path.join(CSRC, "paths.c")).read()
 
 
@@ -274,9 +275,7 @@ def build_driver(tmp_path):
            "-fno-omit-frame-pointer", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
            "-I", "/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
            os.path.join(FAKE, "paths_driver.c"), os.path.join(FAKE, "fake_hip.c"),
-           os.path.join(CSRC, "paths.c"), os.path.join(CSRC, "bhrt_api.c"),
-           os.path.join(CSRC, "particles.c"), os.path.join(CSRC, "kerr_helpers.c"),
-           "-lpthread", "-lm", "-o", exe]
+           os.path.join(CSRC, "paths.c"), *host_core(), "-lpthread", "-lm", "-o", exe]
     subprocess.run(cmd, check=True, capture_output=True, text=True)
     return exe
 

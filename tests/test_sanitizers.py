@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from host_sources import host_core
 
 CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
 
@@ -20,9 +21,7 @@ CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
 def test_host_code_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "asan_driver")
     srcs = [os.path.join(ROOT, "tests", "asan", "asan_driver.c"),
-            os.path.join(ROOT, "oracle", "oracle.c"),
-            os.path.join(CSRC, "bhrt_api.c"), os.path.join(CSRC, "particles.c"),
-            os.path.join(CSRC, "kerr_helpers.c")]
+            os.path.join(ROOT, "oracle", "oracle.c"), *host_core()]
     cmd = ["gcc", "-std=gnu11", "-O1", "-g", "-fsanitize=address,undefined",
            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
            "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(ROOT, "include"),

@@ -1,7 +1,7 @@
 """The trace kernel on scenes off the five baseline configurations (tests/sweep_scenes.py).
 
 The baseline fixes mass 1, spin 0 / 0.9 / 0.99, dt 0.1, distance 100, disk (ISCO, 20), tol 1e-6 /
-1e-8, and the host (bhrt_api.c fill_scene / fill_origin) derives the step-size intervals, the
+1e-8, and the host (scene.c bhrt_fill_scene / bhrt_fill_origin) derives the step-size intervals, the
 far-field switch, the bounded-state and no-evict proofs, the rotation bound, the accept-all
 switch and the sqrt-free disk bounds from exactly those. The sweep moves each of them: 41 scenes,
 70 camera frames of 48x27 and the 181 edge rays of rays_rk4_disk.npz in every scene.
