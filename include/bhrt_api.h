@@ -366,6 +366,69 @@ int bhrt_render_frame_ss(const BlackHoleParams* blackhole, const AccretionDiskPa
                          const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
                          const bhrt_frame_soa* host_out);
 
+/* ---- adaptive supersampled frames: max_samples only at edge pixels ---- */
+
+/* What one adaptive frame did: the shard's pixels, how many of them are edge pixels, the rays
+ * both passes traced (= what bhrt_stats.rays gains), and the pixels of other shards' rows that
+ * were traced for the edge rule alone (0 for a whole image). */
+typedef struct {
+    int64_t pixels, edge_pixels, sample_rays, halo_pixels;
+} bhrt_adaptive_info;
+
+/* (A shard of) a camera frame that gives every pixel as->min_samples samples and only the edge
+ * pixels as->max_samples. THE RULE, with B = as->min_samples, M = as->max_samples, o_s the first M
+ * offsets of bhrt_sample_offsets(ss, as) and c_s(p) the colour of pixel p's sample s under the
+ * frame colour contract:
+ *  1. base(p) = ((...((0.0 + c_0) + c_1) + ...) + c_{B-1}) / B per channel, in IEEE double with
+ *     no contraction;
+ *  2. g(p) starts at 0.0; for each of the 4 neighbours q of p inside the IMAGE (not the shard)
+ *     d = (|base_r(p) - base_r(q)| + |base_g(p) - base_g(q)| + |base_b(p) - base_b(q)|) / 3.0
+ *     with no contraction, and if (d > g) g = d -- a NaN d never raises g, and image-border
+ *     pixels use the neighbours they have;
+ *  3. edge_factor(p) = g(p) > as->edge_threshold ? 1.0 : 0.0 (a NaN threshold: no edges; a
+ *     negative threshold: every pixel an edge);
+ *  4. S(p) is trace_pixel's count with that factor (raytracer.c:1074-1093): B, and where the
+ *     factor exceeds 0.5 min(B + (int)((M - B) * factor), M) = M;
+ *  5. the pixel is ((...((0.0 + c_0) + ...) + c_{S(p)-1}) / S(p): the running SUM continued, not
+ *     the base mean re-weighted; its class is sample 0's, its display fields are the frame's
+ *     conversions of it.
+ * A pixel is a pure function of the image: the same bits run to run, on any stream and in any
+ * row-shard split (a shard traces the base samples of the image rows next to its own, its halo,
+ * for step 2; they are never output). With a negative threshold the frame is
+ * bhrt_render_frame_ss_device's of M samples bit for bit, with +inf or NaN its frame of B.
+ * DEVICE buffers: device_out as for bhrt_render_frame_ss_device (result, all three of
+ * rgb_r/g/b, rgba32f, rgba8), device_samples (may be NULL) S(p) per shard pixel; info (HOST, may
+ * be NULL) is filled before the call returns.
+ * Two trace launches on hip_stream (NULL: ordered like the legacy default stream): the base
+ * samples, then the edge pixels' extra samples (none where there is no edge pixel or M == B).
+ * The size of the second is known only on the device, so the call reads the edge count with one
+ * 8-byte copy and WAITS on the host for the base pass: it is asynchronous only from the second
+ * pass on, and two frames in flight need two host threads or the caller's own interleaving.
+ * bhrt_stats.rays gains info->sample_rays; bhrt_set_claim_order does not apply. Scratch: about
+ * 228 B per base ray (halo included) plus as much per extra ray, in two per-stream blocks.
+ * Returns 0, or -1 with nothing written (bhrt_last_error) for everything
+ * bhrt_render_frame_ss_device refuses, as == NULL or as->enable_adaptive == 0, B < 1, M < B,
+ * M > BHRT_SS_MAX_SAMPLES, width * height or either pass above INT_MAX rays (all of these before
+ * any HIP call), or an allocation or HIP failure. */
+int bhrt_render_frame_adaptive_device(const BlackHoleParams* blackhole,
+                                      const AccretionDiskParams* disk,
+                                      const SimulationConfig* config, const bhrt_camera* camera,
+                                      int width, int height, const bhrt_rows* rows,
+                                      IntegrationMethod method, int flags,
+                                      const SupersamplingParams* ss,
+                                      const AdaptiveSamplingParams* as,
+                                      const bhrt_frame_soa* device_out, int32_t* device_samples,
+                                      bhrt_adaptive_info* info, void* hip_stream);
+
+/* The same whole frame into HOST arrays (host_samples may be NULL), on the current device;
+ * returns when it is complete. */
+int bhrt_render_frame_adaptive(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                               const SimulationConfig* config, const bhrt_camera* camera, int width,
+                               int height, IntegrationMethod method, int flags,
+                               const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
+                               const bhrt_frame_soa* host_out, int32_t* host_samples,
+                               bhrt_adaptive_info* info);
+
 /* Asynchronous form of bhrt_render_frame: queues the frame and returns a ticket (> 0) in
  * *ticket; the host arrays receive the frame through libbhrt's pinned staging (caller memory
  * is never page-locked) and must not be read or freed before bhrt_frame_wait(ticket) returns. Three

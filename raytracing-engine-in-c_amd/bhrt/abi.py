@@ -133,6 +133,12 @@ class Stats(C.Structure):
                 ("attempts_untested", C.c_uint64)]
 
 
+class AdaptiveInfo(C.Structure):
+    """bhrt_adaptive_info: what one adaptive frame did (include/bhrt_api.h)."""
+    _fields_ = [("pixels", C.c_int64), ("edge_pixels", C.c_int64), ("sample_rays", C.c_int64),
+                ("halo_pixels", C.c_int64)]
+
+
 # numpy view of RayTraceHit (160 B, offsets pinned in include/bhrt_types.h)
 HIT_DTYPE = np.dtype({
     "names": ["result", "hit_position", "hit_normal", "distance", "steps", "time_dilation",

@@ -67,6 +67,21 @@ _PROTOS = {
                                        _P(abi.SimulationConfig), _P(abi.Camera), C.c_int, C.c_int,
                                        C.c_int, C.c_int, _P(abi.SupersamplingParams),
                                        _P(abi.AdaptiveSamplingParams), _P(abi.FrameSoA)]),
+    "bhrt_render_frame_adaptive_device": (C.c_int, [_P(abi.BlackHoleParams),
+                                                    _P(abi.AccretionDiskParams),
+                                                    _P(abi.SimulationConfig), _P(abi.Camera),
+                                                    C.c_int, C.c_int, _P(abi.Rows), C.c_int,
+                                                    C.c_int, _P(abi.SupersamplingParams),
+                                                    _P(abi.AdaptiveSamplingParams),
+                                                    _P(abi.FrameSoA), C.c_void_p,
+                                                    _P(abi.AdaptiveInfo), C.c_void_p]),
+    "bhrt_render_frame_adaptive": (C.c_int, [_P(abi.BlackHoleParams),
+                                             _P(abi.AccretionDiskParams),
+                                             _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
+                                             C.c_int, C.c_int, C.c_int,
+                                             _P(abi.SupersamplingParams),
+                                             _P(abi.AdaptiveSamplingParams), _P(abi.FrameSoA),
+                                             C.c_void_p, _P(abi.AdaptiveInfo)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -255,6 +270,42 @@ def render_frame_ss(bh, dk, cfg, cam, width, height, method=abi.INTEGRATOR_RK4, 
     _check(load().bhrt_render_frame_ss(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
                                        method, flags, _ptr(ss), _ptr(as_), C.byref(soa)),
            "bhrt_render_frame_ss")
+    return arrays
+
+
+def _info_dict(info):
+    return {f: int(getattr(info, f)) for f, _ in abi.AdaptiveInfo._fields_}
+
+
+def render_frame_adaptive_device(bh, dk, cfg, cam, width, height, rows, method, flags, ss, as_,
+                                 soa, samples_ptr, stream):
+    """bhrt_render_frame_adaptive_device: (a shard of) a frame with as_.min_samples samples per
+    pixel and as_.max_samples at the edge pixels (the rule: include/bhrt_api.h) into device SoA
+    buffers and, if samples_ptr is not None, the int32 device array of S(p); on a hipStream_t
+    (int handle or None). Returns the call's bhrt_adaptive_info as a dict."""
+    info = abi.AdaptiveInfo()
+    _check(load().bhrt_render_frame_adaptive_device(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam),
+                                                    width, height, _ptr(rows), method, flags,
+                                                    _ptr(ss), _ptr(as_), C.byref(soa),
+                                                    samples_ptr, C.byref(info),
+                                                    C.c_void_p(stream) if stream else None),
+           "bhrt_render_frame_adaptive_device")
+    return _info_dict(info)
+
+
+def render_frame_adaptive(bh, dk, cfg, cam, width, height, method=abi.INTEGRATOR_RK4, flags=0,
+                          ss=None, as_=None, fields=SS_FIELDS):
+    """bhrt_render_frame_adaptive into host numpy arrays (the current device): the fields, plus
+    `samples` (S(p), int32) and `info` (the call's bhrt_adaptive_info as a dict)."""
+    arrays, soa = abi.alloc_soa(width * height, fields)
+    samples = np.zeros(width * height, dtype=np.int32)
+    info = abi.AdaptiveInfo()
+    _check(load().bhrt_render_frame_adaptive(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width,
+                                             height, method, flags, _ptr(ss), _ptr(as_),
+                                             C.byref(soa), samples.ctypes.data, C.byref(info)),
+           "bhrt_render_frame_adaptive")
+    arrays["samples"] = samples
+    arrays["info"] = _info_dict(info)
     return arrays
 
 

@@ -8,7 +8,7 @@
  *   host_frames.c  host-buffer frames in flight, readback, bhrt_trace_rays
  *   batch.c        trace_ray / trace_rays_batch: the pipelined chunks
  *   dropin.c       integrate_photon_path, trace_pixel, the bh_* context API
- *   supersample.c, paths.c, particles.c   features with launchers of their own
+ *   supersample.c, adaptive.c, paths.c, particles.c   features with launchers of their own
  */
 #ifndef BHRT_HOST_H
 #define BHRT_HOST_H
@@ -44,6 +44,12 @@
 #define BHRT_SCRATCH_SLOTS 8
 #define BHRT_FRAME_SLOTS 3  /* host-buffer frames in flight per thread (bhrt_render_frame_async) */
 #define BHRT_COPY_PARTS 4   /* host-buffer frames: a chunk's D2H in parts, each un-permuted as it lands */
+
+typedef struct { /* a growable device block bound to a stream */
+    hipStream_t stream;
+    void* p;
+    size_t cap;
+} bhrt_stream_block;
 
 typedef struct {
     int slot;
@@ -83,12 +89,15 @@ typedef struct {
     size_t cap_hrays;
     /* per-stream launch scratch (ray-array init table + redo list), so launches on different
      * streams never share it; a slot moves to another stream only after its stream drained */
-    struct {
-        hipStream_t stream;
-        void* p;
-        size_t cap;
-    } scratch[BHRT_SCRATCH_SLOTS];
+    bhrt_stream_block scratch[BHRT_SCRATCH_SLOTS];
     int scratch_next;
+    /* a second block per stream (bhrt_stream_keep) for what must outlive a later, larger request
+     * for the launch scratch: an adaptive frame's base planes across its second launch */
+    bhrt_stream_block keep[BHRT_SCRATCH_SLOTS];
+    int keep_next;
+    /* adaptive.c: pinned staging of the edge count read back and the row tables uploaded */
+    void* h_ad;
+    size_t cap_ad;
     /* host-buffer frames (bhrt_render_frame): two trace streams for overlapping chunks, a
      * copy stream, and per chunk: trace finished / its D2H landed */
     hipStream_t stream2, copy;
@@ -152,6 +161,8 @@ int bhrt_ensure(void** p, size_t* cap, size_t need, int pinned);
  * bytes for the same stream returns the same allocation, so a caller that asks for a launch's
  * scratch plus room of its own finds that room behind the launch's part */
 void* bhrt_stream_scratch(devctx_t* c, hipStream_t stream, size_t bytes);
+/* a second block of `stream`, with the same rule, that no bhrt_stream_scratch request moves */
+void* bhrt_stream_keep(devctx_t* c, hipStream_t stream, size_t bytes);
 /* One timed launch with a control block of the ring (kp->ctl, zero at launch; its counters
  * ctl[1..5] are folded into bhrt_stats): the trace kernel (fn NULL), or fn -- a launcher with
  * bhrt_launch_trace's contract and one more argument, named only by the file that passes it, so
@@ -198,6 +209,17 @@ int bhrt_rays_on_device(const Ray* d_rays, const double* d_dirs, int n,
                         const BlackHoleParams* bh, const AccretionDiskParams* dk,
                         const SimulationConfig* cfg, IntegrationMethod method, int flags,
                         const bhrt_frame_soa* out, hipStream_t stream, const Vector3D* origin);
+
+/* ---- supersample.c ---- */
+typedef struct { /* a checked frame: shard pixels, samples per pixel and their offsets */
+    int n, samples;
+    double off_x[BHRT_SS_MAX_SAMPLES], off_y[BHRT_SS_MAX_SAMPLES];
+} bhrt_ss_plan;
+/* a supersampled frame's arguments (bhrt_render_frame_ss_device's refusals): 0 and the plan, or
+ * -1 with the error set; no HIP call */
+int bhrt_ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, const bhrt_camera* cam,
+                  int W, int H, const bhrt_rows* rows, const SupersamplingParams* ss,
+                  const AdaptiveSamplingParams* as, const bhrt_frame_soa* out, bhrt_ss_plan* k);
 
 /* ---- host_frames.c ---- */
 typedef struct {

@@ -167,6 +167,58 @@ typedef struct {
 int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream);
 int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream);
 
+/* Adaptive supersampled frames (adaptive.c; geodesic.hip k_ad_rays, k_ad_edges, k_ad_resolve;
+ * the rule is stated in bhrt_api.h). Rays are addressed by IMAGE pixel: the camera block is the
+ * whole image's (rows = {0, 0, 1}), and the shard enters through two row tables.
+ *   ext rows   the image rows the base pass traces, ascending: the shard's own rows and its
+ *              halo rows; ext pixel q = e * width + px. rows[e] is ext row e's image row and
+ *              ext_of[y] image row y's ext row (or -1); both NULL for a whole image (identity).
+ *   base planes  [B][next] sample-major over the ext pixels, written by the first trace.
+ *   extra planes [M - B][E] over the edge list's slots, written by the second. */
+typedef struct {
+    bhrt_camera_k cam;    /* the whole image's camera; off_x/off_y: the sample's offset, read in
+                             place as k_ss_rays reads its own */
+    int n;                /* rays of this launch                                             */
+    long first;           /* ray r's direction goes to dirs[(first + r) * 3 ..]               */
+    const int* rows;      /* base pass: ray r is ext pixel r (NULL: image pixel r)            */
+    const int* pixels;    /* extra pass: ray r is image pixel pixels[r] (the edge list)       */
+    double* dirs;
+} bhrt_ad_rays_k;
+
+typedef struct {
+    int n, width, height; /* owned pixels; the image                                         */
+    bhrt_rows rows;       /* the shard (num_shards <= 1: whole image)                        */
+    double inv_width, inv_block;
+    const int* ext_of;    /* [height] or NULL                                                */
+    long next;            /* ext pixels: the base planes' stride                             */
+    int base, max;        /* B, M                                                            */
+    double threshold;
+    const double *r, *g, *b; /* base planes                                                  */
+    int* slot;            /* [n] out: the pixel's slot in the edge list, or -1                */
+    int* list;            /* [n] out: slot -> image pixel                                    */
+    unsigned long long* count; /* edge pixels so far (zero at launch)                        */
+} bhrt_ad_edges_k;
+
+typedef struct {
+    int n, width, height;
+    bhrt_rows rows;
+    double inv_width, inv_block;
+    const int* ext_of;
+    long next, nedge;     /* ext pixels; E, the extra planes' stride                          */
+    int base, max;
+    const int32_t* result;   /* base class planes (plane 0 is the pixel's class)               */
+    const double *r, *g, *b; /* base planes                                                  */
+    const double *xr, *xg, *xb; /* extra planes (unused where nedge == 0 or max == base)       */
+    const int* slot;
+    bhrt_frame_soa out;   /* result, rgb_r/g/b, rgba32f, rgba8; NULL fields skipped           */
+    int32_t* samples;     /* S(p), or NULL                                                   */
+} bhrt_ad_resolve_k;
+
+/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+int bhrt_launch_ad_rays(const bhrt_ad_rays_k* k, void* stream);
+int bhrt_launch_ad_edges(const bhrt_ad_edges_k* k, void* stream);
+int bhrt_launch_ad_resolve(const bhrt_ad_resolve_k* k, void* stream);
+
 /* Batched photon paths (paths.c; geodesic.hip k_paths): the launch's bhrt_kparams carries the
  * scene, the AoS rays, n and the control block (ctl[0]: the claim counter, ctl[1..5]: the
  * statistics, as k_trace's; its hit outputs are not used); this block the path outputs. */

@@ -214,26 +214,36 @@ int bhrt_ensure(void** p, size_t* cap, size_t need, int pinned) {
     return 0;
 }
 
-/* launch scratch of `stream` on this context, at least `bytes` */
-void* bhrt_stream_scratch(devctx_t* c, hipStream_t stream, size_t bytes) {
+/* one of the context's per-stream blocks of `stream`, at least `bytes` */
+static void* stream_block(bhrt_stream_block* tab, int* next, hipStream_t stream, size_t bytes) {
     int slot = -1;
     for (int i = 0; i < BHRT_SCRATCH_SLOTS; i++)
-        if (c->scratch[i].p && c->scratch[i].stream == stream) slot = i;
+        if (tab[i].p && tab[i].stream == stream) slot = i;
     if (slot < 0) {
-        slot = c->scratch_next;
-        c->scratch_next = (c->scratch_next + 1) % BHRT_SCRATCH_SLOTS;
-        if (c->scratch[slot].p && hipStreamSynchronize(c->scratch[slot].stream) != hipSuccess) {
+        slot = *next;
+        *next = (*next + 1) % BHRT_SCRATCH_SLOTS;
+        if (tab[slot].p && hipStreamSynchronize(tab[slot].stream) != hipSuccess) {
             set_err("hipStreamSynchronize failed");
             return NULL;
         }
-        c->scratch[slot].stream = stream;
-    } else if (c->scratch[slot].cap < bytes &&
+        tab[slot].stream = stream;
+    } else if (tab[slot].cap < bytes &&
                hipStreamSynchronize(stream) != hipSuccess) { /* in use until drained */
         set_err("hipStreamSynchronize failed");
         return NULL;
     }
-    if (bhrt_ensure(&c->scratch[slot].p, &c->scratch[slot].cap, bytes ? bytes : 64, 0)) return NULL;
-    return c->scratch[slot].p;
+    if (bhrt_ensure(&tab[slot].p, &tab[slot].cap, bytes ? bytes : 64, 0)) return NULL;
+    return tab[slot].p;
+}
+
+/* launch scratch of `stream` on this context, at least `bytes` */
+void* bhrt_stream_scratch(devctx_t* c, hipStream_t stream, size_t bytes) {
+    return stream_block(c->scratch, &c->scratch_next, stream, bytes);
+}
+
+/* the second block of `stream`: never moved or freed by a request for the first */
+void* bhrt_stream_keep(devctx_t* c, hipStream_t stream, size_t bytes) {
+    return stream_block(c->keep, &c->keep_next, stream, bytes);
 }
 
 /* The control ring is zeroed on the GPU, never with a host sync: after a harvest (ring_dirty)

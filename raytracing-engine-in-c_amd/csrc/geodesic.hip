@@ -1939,6 +1939,148 @@ __global__ __launch_bounds__(256) void k_ss_resolve(const bhrt_ss_resolve_k a) {
     if (a.out.result) a.out.result[p] = a.result[p];
 }
 
+// Adaptive supersampled frames (bhrt_kernel.h bhrt_ad_rays_k; the rule: bhrt_api.h). The
+// directions of one sample's rays, one lane per ray, addressed by IMAGE pixel: camera_dir on the
+// whole image's camera, read in place with the sample's offset in it as k_ss_rays reads its own,
+// so the directions are the supersampled frame's bit for bit (test_gpu_adaptive.py).
+__global__ __launch_bounds__(256) void k_ad_rays(const bhrt_ad_rays_k a) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.n) return;  // (the last workgroup's partial wave)
+    int pix = (int)r;
+    if (a.pixels) {
+        pix = a.pixels[r];
+    } else if (a.rows) {
+        const int W = a.cam.width;
+        const int e = div_floor((int)r, W, a.cam.inv_width);
+        pix = a.rows[e] * W + ((int)r - e * W);
+    }
+    double dx, dy, dz;
+    camera_dir(a.cam, pix, dx, dy, dz);
+    double* d = a.dirs + ((size_t)a.first + (size_t)r) * 3;
+    d[0] = dx;
+    d[1] = dy;
+    d[2] = dz;
+}
+
+// shard pixel p's image column and row (camera_dir's own mapping)
+__device__ __forceinline__ void ad_pixel(int p, int W, const bhrt_rows& rows, double inv_width,
+                                         double inv_block, int& px, int& py) {
+    const int j = div_floor(p, W, inv_width);
+    px = p - j * W;
+    py = j;
+    if (rows.num_shards > 1) {
+        const int B = rows.row_block;
+        const int jb = div_floor(j, B, inv_block);
+        py = (jb * rows.num_shards + rows.shard) * B + (j - jb * B);
+    }
+}
+
+// step 1 of the rule: the base colour of ext pixel q
+__device__ __forceinline__ void ad_base(const double* pr, const double* pg, const double* pb,
+                                        size_t next, int B, size_t q, double& r, double& g,
+                                        double& b) {
+#pragma clang fp contract(off)
+    r = g = b = 0.0;
+    for (int s = 0; s < B; s++) {
+        const size_t i = (size_t)s * next + q;
+        r = r + pr[i];
+        g = g + pg[i];
+        b = b + pb[i];
+    }
+    const double nb = (double)B;
+    r = r / nb;
+    g = g / nb;
+    b = b / nb;
+}
+
+// Steps 2 to 4, one lane per owned pixel: the edge value over the 4-neighbourhood in the image,
+// the decision, and the edge pixels compacted into a list -- per wave one ballot, the lane's
+// rank among the set bits below it, and ONE returning atomic on the counter. The slot order
+// follows the waves' arrival and differs from run to run; nothing downstream depends on it (a
+// pixel finds its extra samples through its own slot).
+__global__ __launch_bounds__(256) void k_ad_edges(const bhrt_ad_edges_k a) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = p < a.n;  // (no early exit: the whole wave takes part in the ballot)
+    bool edge = false;
+    int pix = 0;
+    if (live) {
+        const int W = a.width;
+        int px, py;
+        ad_pixel((int)p, W, a.rows, a.inv_width, a.inv_block, px, py);
+        pix = py * W + px;
+        const size_t next = (size_t)a.next;
+        const int e = a.ext_of ? a.ext_of[py] : py;
+        double r, g, b;
+        ad_base(a.r, a.g, a.b, next, a.base, (size_t)e * W + px, r, g, b);
+        double gmax = 0.0;
+        for (int k = 0; k < 4; k++) {
+            const int qx = px + (k == 0 ? -1 : (k == 1 ? 1 : 0));
+            const int qy = py + (k == 2 ? -1 : (k == 3 ? 1 : 0));
+            if (qx < 0 || qx >= W || qy < 0 || qy >= a.height) continue;
+            const int qe = a.ext_of ? a.ext_of[qy] : qy;
+            if (qe < 0) continue;  // (never: a shard's ext rows hold its rows' vertical neighbours)
+            double qr, qg, qb;
+            ad_base(a.r, a.g, a.b, next, a.base, (size_t)qe * W + qx, qr, qg, qb);
+            const double d = (fabs(r - qr) + fabs(g - qg) + fabs(b - qb)) / 3.0;
+            if (d > gmax) gmax = d;  // (false for a NaN d)
+        }
+        edge = gmax > a.threshold;  // (false for a NaN threshold)
+    }
+    const unsigned long long m = __ballot(edge);
+    int slot = -1;
+    if (m) {  // (wave-uniform)
+        const int lane = (int)(threadIdx.x & 63u), leader = __ffsll((long long)m) - 1;
+        int first = 0;
+        if (lane == leader) first = (int)atomicAdd(a.count, (unsigned long long)__popcll(m));
+        first = __shfl(first, leader);
+        if (edge) {
+            slot = first + __popcll(m & ((1ull << lane) - 1ull));
+            a.list[slot] = pix;
+        }
+    }
+    if (live) a.slot[p] = slot;
+}
+
+// Step 5, one lane per owned pixel: the sequential sum over the base planes continued over the
+// pixel's extra samples (through its slot), divided by S(p); the outputs as store_colour
+// converts them, sample 0's class, and S(p).
+__global__ __launch_bounds__(256) void k_ad_resolve(const bhrt_ad_resolve_k a) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.n) return;  // (the last workgroup's partial wave)
+    const int W = a.width;
+    int px, py;
+    ad_pixel((int)p, W, a.rows, a.inv_width, a.inv_block, px, py);
+    const int e = a.ext_of ? a.ext_of[py] : py;
+    const size_t q = (size_t)e * W + px, next = (size_t)a.next;
+    double r = 0.0, g = 0.0, b = 0.0;
+    for (int s = 0; s < a.base; s++) {
+        const size_t i = (size_t)s * next + q;
+        r = r + a.r[i];
+        g = g + a.g[i];
+        b = b + a.b[i];
+    }
+    const int slot = a.slot[p];
+    int S = a.base;
+    if (slot >= 0) {
+        S = a.max;
+        for (int s = 0; s < a.max - a.base; s++) {
+            const size_t i = (size_t)s * (size_t)a.nedge + (size_t)slot;
+            r = r + a.xr[i];
+            g = g + a.xg[i];
+            b = b + a.xb[i];
+        }
+    }
+    const double ns = (double)S;
+    r = r / ns;
+    g = g / ns;
+    b = b / ns;
+    store_colour(a.out, (int)p, r, g, b);
+    if (a.out.result) a.out.result[p] = a.result[q];
+    if (a.samples) a.samples[p] = S;
+}
+
 // integrate_photon_path with a recorded path (one ray, one lane). The output hit goes to
 // element 0 of kp.out; the path and the stored-point count to path / d_num.
 template <int METHOD, bool SPIN0>
@@ -2475,6 +2617,27 @@ extern "C" int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream) {
 extern "C" int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream) {
     if (k->n <= 0 || k->samples <= 0) return 0;
     k_ss_resolve<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
+                   static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ad_rays(const bhrt_ad_rays_k* k, void* stream) {
+    if (k->n <= 0 || k->first < 0) return 0;
+    k_ad_rays<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
+                static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ad_edges(const bhrt_ad_edges_k* k, void* stream) {
+    if (k->n <= 0 || k->base <= 0) return 0;
+    k_ad_edges<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
+                 static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ad_resolve(const bhrt_ad_resolve_k* k, void* stream) {
+    if (k->n <= 0 || k->base <= 0) return 0;
+    k_ad_resolve<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
                    static_cast<hipStream_t>(stream)>>>(*k);
     return (int)hipGetLastError();
 }

@@ -61,16 +61,12 @@ int bhrt_sample_offsets(const SupersamplingParams* ss, const AdaptiveSamplingPar
  * rgb_r/g/b (10..12), rgba32f (13), rgba8 (14) */
 #define SS_FIELDS 0x7c01u
 
-typedef struct { /* a checked frame: shard pixels, samples per pixel and their offsets */
-    int n, samples;
-    double off_x[BHRT_SS_MAX_SAMPLES], off_y[BHRT_SS_MAX_SAMPLES];
-} ss_plan;
+typedef bhrt_ss_plan ss_plan;
 
-/* the frame's arguments: 0 and the plan, or -1 */
-static int ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, const bhrt_camera* cam,
-                    int W, int H, const bhrt_rows* rows, const SupersamplingParams* ss,
-                    const AdaptiveSamplingParams* as, const bhrt_frame_soa* out,
-                    ss_plan* k) {
+/* the frame's arguments: 0 and the plan, or -1 (no HIP call) */
+int bhrt_ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, const bhrt_camera* cam,
+                  int W, int H, const bhrt_rows* rows, const SupersamplingParams* ss,
+                  const AdaptiveSamplingParams* as, const bhrt_frame_soa* out, ss_plan* k) {
     if (!bh || !cfg || !cam || !out || W <= 0 || H <= 0) {
         bhrt_set_err("supersampled frame: invalid argument");
         return -1;
@@ -209,7 +205,7 @@ int bhrt_render_frame_ss_device(const BlackHoleParams* bh, const AccretionDiskPa
                                 const SupersamplingParams* ss, const AdaptiveSamplingParams* as,
                                 const bhrt_frame_soa* out, void* stream) {
     ss_plan k;
-    if (ss_check(bh, cfg, cam, W, H, rows, ss, as, out, &k)) return -1;
+    if (bhrt_ss_check(bh, cfg, cam, W, H, rows, ss, as, out, &k)) return -1;
     devctx_t* c = bhrt_ctx_get(bhrt_current_device());
     if (!c) return -1;
     /* NULL stream: the kernels run on libbhrt's own stream, after the caller's default-stream
@@ -223,7 +219,7 @@ int bhrt_render_frame_ss(const BlackHoleParams* bh, const AccretionDiskParams* d
                          IntegrationMethod method, int flags, const SupersamplingParams* ss,
                          const AdaptiveSamplingParams* as, const bhrt_frame_soa* out) {
     ss_plan k;
-    if (ss_check(bh, cfg, cam, W, H, NULL, ss, as, out, &k)) return -1;
+    if (bhrt_ss_check(bh, cfg, cam, W, H, NULL, ss, as, out, &k)) return -1;
     const int n = k.n;
     devctx_t* c = bhrt_ctx_get(bhrt_current_device());
     if (!c || bhrt_ctx_streams(c)) return -1;
