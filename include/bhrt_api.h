@@ -429,6 +429,126 @@ int bhrt_render_frame_adaptive(const BlackHoleParams* blackhole, const Accretion
                                const bhrt_frame_soa* host_out, int32_t* host_samples,
                                bhrt_adaptive_info* info);
 
+/* ---- temporal accumulation: one jittered sample per pixel per frame, blended on the GPU ---- */
+
+/* The visualizer's temporal path (TemporalAccumulationBuffer, renderer.h:39-48; accumulateFrame,
+ * detectEdges, finalizeAccumulatedFrame, renderer.cpp:1759-1877) as an object on the device: every
+ * frame is a plain camera frame at the next sub-pixel offset of a sample set, blended into a
+ * running image. THE RULE -- all arithmetic is IEEE float32 with no contraction.
+ * State of an accumulator of n pixels (a W x H image, or a bhrt_rows shard of it): acc[n][3] = 0,
+ * edge[n] = 0, frame_count = 0, jitter_index = 0, reset_pending = 1. One step with a new frame
+ * f[n][3]:
+ *  1. if reset_pending: acc = 0, frame_count = 0, reset_pending = 0 (edge and jitter_index are
+ *     kept, as resetAccumulation keeps them);
+ *  2. alpha = bhrt_accum_alpha(params, frame_count): BHRT_ACCUM_REFERENCE 1.0f at frame_count 0,
+ *     0.5f below 5, else blend_factor; BHRT_ACCUM_MEAN 1.0f / (float)(frame_count + 1), a running
+ *     mean until max_frames caps frame_count and an exponential average from there;
+ *  3. w = 1.0f - alpha (rounded once) and acc[i] = acc[i] * w + f[i] * alpha: two products and one
+ *     sum. A NaN colour stays NaN until the next reset;
+ *  4. frame_count = min(frame_count + 1, max_frames); jitter_index = (jitter_index + 1) % cycle;
+ *  5. edges, whole images only, interior pixels 1..W-2 x 1..H-2, on the NEW acc: for the
+ *     neighbours up, down, left and right d = (((0 + |dr|) + |dg|) + |db|) / 3.0f, g the largest d
+ *     by `if (d > g) g = d` from 0 (a NaN d never raises it), and
+ *     edge = g > edge_threshold ? 1.0f : max(0.0f, edge - edge_decay); border pixels stay 0;
+ *  6. display rgba8: c' = max(0.0f, min(1.0f, c)) as std::max / std::min evaluate it (NaN -> 1),
+ *     (unsigned char)(pow(c', 1.0f / 2.2f) * 255.0f) truncated toward zero, alpha byte 255, row 0 =
+ *     the top image row. The power is the double pow of (double)c' and (double)(1.0f / 2.2f)
+ *     rounded to float (the reference's float overload may differ from it by one byte step where
+ *     the product lies within 255 * 16 * 2^-24 of an integer).
+ * A rendered step takes f = (float) of the frame colour contract's rgb (what rgba32f holds) of the
+ * plain camera frame whose offset is sample jitter_index (its value BEFORE step 4) of
+ * bhrt_sample_offsets(ss, NULL), cycle = that call's count; ss == NULL or one sample: the pixel
+ * centres every frame, cycle 1. Deviations from the reference: DESIGN.md section 14. */
+typedef enum { BHRT_ACCUM_REFERENCE = 0, BHRT_ACCUM_MEAN = 1 } bhrt_accum_schedule;
+
+typedef struct {
+    int32_t schedule;        /* bhrt_accum_schedule                      default REFERENCE */
+    float   blend_factor;    /* REFERENCE: alpha from frame_count 5 on            0.1f     */
+    int32_t max_frames;      /* cap of frame_count                                32       */
+    float   edge_threshold;  /* NaN: no edges                                     0.1f     */
+    float   edge_decay;      /*                                                   0.2f     */
+} bhrt_accum_params;         /* (initTemporalBuffer, renderer.cpp:1732-1739, :1842-1849)    */
+
+typedef struct bhrt_accum bhrt_accum; /* opaque; owned by the thread and device that made it */
+
+typedef struct {
+    int32_t frame_count, jitter_index;
+    int32_t reset_pending;   /* the next step starts from acc = 0                          */
+    int32_t cycle;           /* count of bhrt_sample_offsets(ss, NULL) for bhrt_accum_info's ss */
+    float   next_alpha;      /* the next step's alpha (1.0f where reset_pending)           */
+    int32_t sharded;         /* a row shard: no edge factors                               */
+    double  next_offset_x, next_offset_y; /* the next rendered step's sub-pixel offset     */
+    int64_t frames_total;    /* steps since creation, resets not counted off               */
+    int64_t pixels;          /* n                                                          */
+} bhrt_accum_state;
+
+typedef struct {             /* DEVICE buffers (HOST for bhrt_accum_frame); any may be NULL */
+    uint8_t* rgba8;          /* [n][4] step 6                                              */
+    float*   rgb;            /* [n][3] a copy of the new acc                               */
+    float*   edge_factor;    /* [n] the new edge; whole images only                        */
+} bhrt_accum_out;
+
+/* Step 2's alpha for these parameters (NULL: the defaults) at this frame_count. Host only. */
+float bhrt_accum_alpha(const bhrt_accum_params* params, int frame_count);
+
+/* An accumulator for (the shard `rows` of) a width x height image on the CURRENT device: 28 B of
+ * state and 16 B of frame scratch per pixel. params NULL: the defaults. Returns 0 and the handle
+ * in *acc, or -1 with *acc untouched (bhrt_last_error): before any HIP call for a NULL acc, width
+ * or height < 1, a bad row sharding, more than INT_MAX pixels, an unknown schedule, blend_factor
+ * NaN or outside [0, 1], max_frames < 1, a negative or NaN edge_decay (a NaN edge_threshold is
+ * valid: no edges); or an allocation or HIP failure. Waits for the device buffers' zero fill. */
+int bhrt_accum_create(int width, int height, const bhrt_rows* rows, const bhrt_accum_params* params,
+                      bhrt_accum** acc);
+
+/* Frees the accumulator once the device has finished with it (waits for the device). NULL: no-op. */
+void bhrt_accum_destroy(bhrt_accum* acc);
+
+/* Sets reset_pending: what the viewer does on a camera or parameter change. 0, or -1 for NULL. */
+int bhrt_accum_reset(bhrt_accum* acc);
+
+/* The host-side state, with cycle and the next offset for `ss` (NULL: pixel centres). 0, or -1
+ * (state untouched) for a NULL argument or a bhrt_sample_offsets refusal. No HIP call. */
+int bhrt_accum_info(const bhrt_accum* acc, const SupersamplingParams* ss, bhrt_accum_state* state);
+
+/* The accumulator's own device arrays, for zero-copy reading in stream order after a step:
+ * *device_rgb = acc [n][3] float, *device_edge = edge [n] float (either pointer may be NULL). */
+int bhrt_accum_device_buffers(const bhrt_accum* acc, const float** device_rgb,
+                              const float** device_edge);
+
+/* One rendered step: the plain camera frame at the next offset (the launch of
+ * bhrt_render_frame_device with the offset in the camera, writing rgba32f into the accumulator's
+ * scratch), then steps 1 to 6 in two small kernels, all on hip_stream. Asynchronous with NO host
+ * wait: several frames can be in flight from one thread. NULL hip_stream is ordered like the legacy
+ * default stream, exactly as for bhrt_render_frame_device. The host-side state (frame_count,
+ * jitter_index, reset_pending, frames_total) advances AT THE CALL; the device work is stream-ordered.
+ * The frames of one accumulator share its scratch frame and its state arrays, so THE CALLER ORDERS
+ * THEM: the same stream for every step of an accumulator, or the caller's own events between the
+ * streams it uses. bhrt_stats.rays gains n per frame; bhrt_set_claim_order applies as for the plain
+ * frame. Returns 0, or -1 with nothing written and the state unchanged (bhrt_last_error), before
+ * any HIP call for: a NULL acc, blackhole, config, camera or device_out; camera->use_offset != 0
+ * (the accumulator sets the offsets); a bhrt_sample_offsets refusal (JITTER_RANDOM with more than
+ * one sample, more than BHRT_SS_MAX_SAMPLES samples); device_out->edge_factor from a shard
+ * accumulator; a current device other than the accumulator's; and for a HIP failure. */
+int bhrt_accum_frame_device(bhrt_accum* acc, const BlackHoleParams* blackhole,
+                            const AccretionDiskParams* disk, const SimulationConfig* config,
+                            const bhrt_camera* camera, IntegrationMethod method, int flags,
+                            const SupersamplingParams* ss, const bhrt_accum_out* device_out,
+                            void* hip_stream);
+
+/* accumulateFrame of the caller's own DEVICE frame device_rgb [n][3] float, then the same steps 4
+ * to 6 with cycle = BHRT_SS_MAX_SAMPLES, the reference's literal 64 (a rendered step that finds
+ * jitter_index at or above its own cycle takes it modulo that cycle first). Stream and state
+ * rules as above; device_out may be NULL here (the state arrays alone are updated). */
+int bhrt_accum_blend_device(bhrt_accum* acc, const float* device_rgb,
+                            const bhrt_accum_out* device_out, void* hip_stream);
+
+/* bhrt_accum_frame_device into HOST arrays, on the current device; returns when they are
+ * complete. */
+int bhrt_accum_frame(bhrt_accum* acc, const BlackHoleParams* blackhole,
+                     const AccretionDiskParams* disk, const SimulationConfig* config,
+                     const bhrt_camera* camera, IntegrationMethod method, int flags,
+                     const SupersamplingParams* ss, const bhrt_accum_out* host_out);
+
 /* Asynchronous form of bhrt_render_frame: queues the frame and returns a ticket (> 0) in
  * *ticket; the host arrays receive the frame through libbhrt's pinned staging (caller memory
  * is never page-locked) and must not be read or freed before bhrt_frame_wait(ticket) returns. Three

@@ -139,6 +139,34 @@ class AdaptiveInfo(C.Structure):
                 ("halo_pixels", C.c_int64)]
 
 
+# temporal accumulation (include/bhrt_api.h)
+BHRT_ACCUM_REFERENCE, BHRT_ACCUM_MEAN = 0, 1
+
+
+class AccumParams(C.Structure):
+    """bhrt_accum_params; AccumParams() holds the defaults of initTemporalBuffer."""
+    _fields_ = [("schedule", C.c_int32), ("blend_factor", C.c_float), ("max_frames", C.c_int32),
+                ("edge_threshold", C.c_float), ("edge_decay", C.c_float)]
+
+    def __init__(self, schedule=BHRT_ACCUM_REFERENCE, blend_factor=0.1, max_frames=32,
+                 edge_threshold=0.1, edge_decay=0.2):
+        super().__init__(schedule, blend_factor, max_frames, edge_threshold, edge_decay)
+
+
+class AccumState(C.Structure):
+    """bhrt_accum_state: the host-side state of an accumulator."""
+    _fields_ = [("frame_count", C.c_int32), ("jitter_index", C.c_int32),
+                ("reset_pending", C.c_int32), ("cycle", C.c_int32), ("next_alpha", C.c_float),
+                ("sharded", C.c_int32), ("next_offset_x", C.c_double),
+                ("next_offset_y", C.c_double), ("frames_total", C.c_int64),
+                ("pixels", C.c_int64)]
+
+
+class AccumOut(C.Structure):
+    """bhrt_accum_out: rgba8 [n][4] uint8, rgb [n][3] float32, edge_factor [n] float32."""
+    _fields_ = [("rgba8", C.c_void_p), ("rgb", C.c_void_p), ("edge_factor", C.c_void_p)]
+
+
 # numpy view of RayTraceHit (160 B, offsets pinned in include/bhrt_types.h)
 HIT_DTYPE = np.dtype({
     "names": ["result", "hit_position", "hit_normal", "distance", "steps", "time_dilation",

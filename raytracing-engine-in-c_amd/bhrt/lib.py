@@ -82,6 +82,23 @@ _PROTOS = {
                                              _P(abi.SupersamplingParams),
                                              _P(abi.AdaptiveSamplingParams), _P(abi.FrameSoA),
                                              C.c_void_p, _P(abi.AdaptiveInfo)]),
+    "bhrt_accum_alpha": (C.c_float, [_P(abi.AccumParams), C.c_int]),
+    "bhrt_accum_create": (C.c_int, [C.c_int, C.c_int, _P(abi.Rows), _P(abi.AccumParams),
+                                    _P(C.c_void_p)]),
+    "bhrt_accum_destroy": (None, [C.c_void_p]),
+    "bhrt_accum_reset": (C.c_int, [C.c_void_p]),
+    "bhrt_accum_info": (C.c_int, [C.c_void_p, _P(abi.SupersamplingParams), _P(abi.AccumState)]),
+    "bhrt_accum_device_buffers": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "bhrt_accum_frame_device": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
+                                          _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                          _P(abi.Camera), C.c_int, C.c_int,
+                                          _P(abi.SupersamplingParams), _P(abi.AccumOut),
+                                          C.c_void_p]),
+    "bhrt_accum_blend_device": (C.c_int, [C.c_void_p, C.c_void_p, _P(abi.AccumOut), C.c_void_p]),
+    "bhrt_accum_frame": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
+                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                   _P(abi.Camera), C.c_int, C.c_int, _P(abi.SupersamplingParams),
+                                   _P(abi.AccumOut)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -306,6 +323,81 @@ def render_frame_adaptive(bh, dk, cfg, cam, width, height, method=abi.INTEGRATOR
            "bhrt_render_frame_adaptive")
     arrays["samples"] = samples
     arrays["info"] = _info_dict(info)
+    return arrays
+
+
+def accum_alpha(params, frame_count):
+    """bhrt_accum_alpha: the blend weight of the step at this frame_count (params None: the
+    defaults), as the float32 the library uses."""
+    return np.float32(load().bhrt_accum_alpha(_ptr(params), int(frame_count)))
+
+
+def accum_create(width, height, rows=None, params=None):
+    """bhrt_accum_create on the current device: the handle (an int) for the accum_* calls; free
+    it with accum_destroy."""
+    h = C.c_void_p()
+    _check(load().bhrt_accum_create(int(width), int(height), _ptr(rows), _ptr(params),
+                                    C.byref(h)), "bhrt_accum_create")
+    return h.value
+
+
+def accum_destroy(acc):
+    load().bhrt_accum_destroy(acc)
+
+
+def accum_reset(acc):
+    """bhrt_accum_reset: the next step starts from an empty image."""
+    _check(load().bhrt_accum_reset(acc), "bhrt_accum_reset")
+
+
+def accum_state(acc, ss=None):
+    """bhrt_accum_info: the host-side state as a dict (cycle and the next offset for `ss`)."""
+    s = abi.AccumState()
+    _check(load().bhrt_accum_info(acc, _ptr(ss), C.byref(s)), "bhrt_accum_info")
+    return {f: getattr(s, f) for f, _ in abi.AccumState._fields_}
+
+
+def accum_device_buffers(acc):
+    """bhrt_accum_device_buffers: (acc [n][3] float32, edge [n] float32) device addresses."""
+    rgb, edge = C.c_void_p(), C.c_void_p()
+    _check(load().bhrt_accum_device_buffers(acc, C.byref(rgb), C.byref(edge)),
+           "bhrt_accum_device_buffers")
+    return rgb.value, edge.value
+
+
+def accum_out(tensors):
+    """abi.AccumOut pointing at device tensors (torch) keyed rgba8 / rgb / edge_factor."""
+    return abi.AccumOut(**{f: t.data_ptr() for f, t in tensors.items()})
+
+
+def accum_frame_device(acc, bh, dk, cfg, cam, method, flags, ss, out, stream):
+    """bhrt_accum_frame_device: one rendered step of the accumulator -- the plain frame at the
+    next offset of `ss`, blended, with the display bytes and edge factors -- into the device
+    buffers of `out` (abi.AccumOut), asynchronous on a hipStream_t (int handle or None)."""
+    _check(load().bhrt_accum_frame_device(acc, _ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), method,
+                                          flags, _ptr(ss), _ptr(out),
+                                          C.c_void_p(stream) if stream else None),
+           "bhrt_accum_frame_device")
+
+
+def accum_blend_device(acc, rgb_ptr, out, stream):
+    """bhrt_accum_blend_device: one step with the caller's device frame ([n][3] float32 at
+    rgb_ptr); `out` may be None."""
+    _check(load().bhrt_accum_blend_device(acc, rgb_ptr, _ptr(out),
+                                          C.c_void_p(stream) if stream else None),
+           "bhrt_accum_blend_device")
+
+
+def accum_frame(acc, bh, dk, cfg, cam, method=abi.INTEGRATOR_RK4, flags=0, ss=None,
+                fields=("rgba8", "rgb", "edge_factor")):
+    """bhrt_accum_frame: one rendered step into host numpy arrays (a dict of `fields`)."""
+    n = accum_state(acc)["pixels"]
+    shape = {"rgba8": ((n, 4), np.uint8), "rgb": ((n, 3), np.float32),
+             "edge_factor": ((n,), np.float32)}
+    arrays = {f: np.zeros(*shape[f]) for f in fields}
+    out = abi.AccumOut(**{f: a.ctypes.data for f, a in arrays.items()})
+    _check(load().bhrt_accum_frame(acc, _ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), method, flags,
+                                   _ptr(ss), C.byref(out)), "bhrt_accum_frame")
     return arrays
 
 

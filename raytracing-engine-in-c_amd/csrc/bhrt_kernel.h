@@ -219,6 +219,35 @@ int bhrt_launch_ad_rays(const bhrt_ad_rays_k* k, void* stream);
 int bhrt_launch_ad_edges(const bhrt_ad_edges_k* k, void* stream);
 int bhrt_launch_ad_resolve(const bhrt_ad_resolve_k* k, void* stream);
 
+/* Temporal accumulation (temporal.c; geodesic.hip k_ta_blend, k_ta_edges; the rule is stated in
+ * bhrt_api.h). Two elementwise kernels behind the unchanged camera-frame launch: the blend with
+ * the display conversion, then -- whole images only -- the edge stencil on the UPDATED acc, a
+ * launch of its own because the blend updates acc in place (a lane that recomputed its
+ * neighbours' blends would race with their stores unless acc were kept twice). */
+typedef struct {
+    long n;               /* pixels                                                          */
+    const float* frame;   /* the new frame: [n][4] (the trace's rgba32f) or [n][3]            */
+    int stride;           /* 4 or 3                                                          */
+    int zero;             /* step 1: acc counts as 0.0f, whatever the array holds             */
+    float alpha, w;       /* step 2's alpha and w = 1.0f - alpha, rounded on the host          */
+    float* acc;           /* [n][3] in place                                                 */
+    float* rgb;           /* [n][3] copy of the new acc, or NULL                              */
+    uint8_t* rgba8;       /* [n][4] step 6, or NULL                                           */
+} bhrt_ta_blend_k;
+
+typedef struct {
+    long n;               /* width * height                                                  */
+    int width, height;
+    float threshold, decay;
+    const float* acc;     /* [n][3] the updated acc                                          */
+    float* edge;          /* [n] in place (border pixels are never written: they stay 0)       */
+    float* out;           /* [n] copy of the new edge, or NULL                                */
+} bhrt_ta_edges_k;
+
+/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+int bhrt_launch_ta_blend(const bhrt_ta_blend_k* k, void* stream);
+int bhrt_launch_ta_edges(const bhrt_ta_edges_k* k, void* stream);
+
 /* Batched photon paths (paths.c; geodesic.hip k_paths): the launch's bhrt_kparams carries the
  * scene, the AoS rays, n and the control block (ctl[0]: the claim counter, ctl[1..5]: the
  * statistics, as k_trace's; its hit outputs are not used); this block the path outputs. */

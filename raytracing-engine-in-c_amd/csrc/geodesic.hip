@@ -2081,6 +2081,87 @@ __global__ __launch_bounds__(256) void k_ad_resolve(const bhrt_ad_resolve_k a) {
     if (a.samples) a.samples[p] = S;
 }
 
+// Temporal accumulation (bhrt_kernel.h bhrt_ta_blend_k; the rule: bhrt_api.h). All float32, no
+// contraction, as the reference's x86 build evaluates accumulateFrame, detectEdges and
+// finalizeAccumulatedFrame (renderer.cpp:1759-1877).
+struct ta_f3 {  // 12 bytes, 4-byte aligned: one dwordx3 load or store
+    float x, y, z;
+};
+
+// Step 6 of one channel, the ONE place that decides the gamma: std::min / std::max as the
+// reference calls them (NaN -> 1.0f, -0.0f -> 0.0f), then the DOUBLE pow of the float operands
+// rounded to float -- within a double ulp of the exact power, so the float is the correctly
+// rounded one but for ties no image meets, where powf's 1-ulp result would move the truncation
+// at every byte boundary it straddles -- times 255.0f, truncated toward zero.
+__device__ __forceinline__ unsigned ta_gamma_u8(float c) {
+#pragma clang fp contract(off)
+    const float m = (c < 1.0f) ? c : 1.0f;
+    const float k = (0.0f < m) ? m : 0.0f;
+    const float g = (float)pow((double)k, (double)(1.0f / 2.2f));
+    return (unsigned)(int)(g * 255.0f) & 0xffu;
+}
+
+// Steps 1 to 3 and 6, one lane per pixel: a 16-byte (the trace's rgba32f) or 12-byte (a caller's
+// frame) load of the new colour, a 12-byte load and store of acc, the optional 12-byte copy and
+// one packed 4-byte rgba8 store. Step 1's zeroing is a select, not a fill.
+__global__ __launch_bounds__(256) void k_ta_blend(const bhrt_ta_blend_k a) {
+#pragma clang fp contract(off)
+    const size_t p = (size_t)blockIdx.x * 256 + (size_t)threadIdx.x;
+    if (p >= (size_t)a.n) return;  // (the last workgroup's partial wave)
+    ta_f3 f;
+    if (a.stride == 4) {
+        const float4 v = reinterpret_cast<const float4*>(a.frame)[p];
+        f.x = v.x;
+        f.y = v.y;
+        f.z = v.z;
+    } else {
+        f = reinterpret_cast<const ta_f3*>(a.frame)[p];
+    }
+    ta_f3* acc = reinterpret_cast<ta_f3*>(a.acc) + p;
+    ta_f3 c = {0.0f, 0.0f, 0.0f};
+    if (!a.zero) c = *acc;
+    c.x = c.x * a.w + f.x * a.alpha;
+    c.y = c.y * a.w + f.y * a.alpha;
+    c.z = c.z * a.w + f.z * a.alpha;
+    *acc = c;
+    if (a.rgb) reinterpret_cast<ta_f3*>(a.rgb)[p] = c;
+    if (a.rgba8)
+        reinterpret_cast<unsigned*>(a.rgba8)[p] =
+            ta_gamma_u8(c.x) | (ta_gamma_u8(c.y) << 8) | (ta_gamma_u8(c.z) << 16) | 0xff000000u;
+}
+
+// Step 5, one lane per pixel of a whole image, launched behind k_ta_blend on the same stream: the
+// stencil reads the UPDATED acc of the four neighbours (mostly from the L2 the blend just wrote).
+// Border pixels never touch edge[] (it stays 0 from creation) and report 0.
+__global__ __launch_bounds__(256) void k_ta_edges(const bhrt_ta_edges_k a) {
+#pragma clang fp contract(off)
+    const size_t p = (size_t)blockIdx.x * 256 + (size_t)threadIdx.x;
+    if (p >= (size_t)a.n) return;  // (the last workgroup's partial wave)
+    const unsigned W = (unsigned)a.width, H = (unsigned)a.height;
+    const unsigned y = (unsigned)p / W, x = (unsigned)p - y * W;  // (n <= INT_MAX)
+    float e = 0.0f;
+    if (x >= 1u && x + 1u < W && y >= 1u && y + 1u < H) {
+        const ta_f3* A = reinterpret_cast<const ta_f3*>(a.acc);
+        const ta_f3 c = A[p];
+        const size_t q[4] = {p - (size_t)W, p + (size_t)W, p - 1, p + 1};
+        float g = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const ta_f3 v = A[q[k]];
+            float d = 0.0f;
+            d = d + fabsf(c.x - v.x);
+            d = d + fabsf(c.y - v.y);
+            d = d + fabsf(c.z - v.z);
+            d = d / 3.0f;
+            if (d > g) g = d;  // (false for a NaN d)
+        }
+        const float dec = a.edge[p] - a.decay;
+        e = (g > a.threshold) ? 1.0f : ((0.0f < dec) ? dec : 0.0f);  // (NaN threshold: decay)
+        a.edge[p] = e;
+    }
+    if (a.out) a.out[p] = e;
+}
+
 // integrate_photon_path with a recorded path (one ray, one lane). The output hit goes to
 // element 0 of kp.out; the path and the stored-point count to path / d_num.
 template <int METHOD, bool SPIN0>
@@ -2639,6 +2720,19 @@ extern "C" int bhrt_launch_ad_resolve(const bhrt_ad_resolve_k* k, void* stream) 
     if (k->n <= 0 || k->base <= 0) return 0;
     k_ad_resolve<<<(unsigned)(((long)k->n + 255) / 256), 256, 0,
                    static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+// (exact grids with a tail guard; n <= INT_MAX, so the workgroup count fits an unsigned)
+extern "C" int bhrt_launch_ta_blend(const bhrt_ta_blend_k* k, void* stream) {
+    if (k->n <= 0 || (k->stride != 3 && k->stride != 4)) return 0;
+    k_ta_blend<<<(unsigned)((k->n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(*k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_ta_edges(const bhrt_ta_edges_k* k, void* stream) {
+    if (k->n <= 0 || k->width <= 0 || k->n != (long)k->width * k->height) return 0;
+    k_ta_edges<<<(unsigned)((k->n + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(*k);
     return (int)hipGetLastError();
 }
 
