@@ -633,6 +633,18 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* blackhole,
 int bhrt_check_rkf45_accept(const double* err, const double* scale, const double* tol, int n,
                             int* out, void* hip_stream);
 
+/* Diagnostic: the trace loop's disk decision (geodesic.hip disk_hit) on n cases of DEVICE arrays
+ * p[3n] (the point), d[3n] (the direction) and nrm[3n] (the plane "normal": the previous path
+ * point), against the squared-radius thresholds in_sq <= s <= out_sq; d_out[i] = 1 for a hit.
+ * Returns 0 or a hipError_t value; asynchronous on hip_stream. */
+int bhrt_check_disk_hit(const double* p, const double* d, const double* nrm, int n, double in_sq,
+                        double out_sq, int* out, void* hip_stream);
+
+/* Diagnostic: the square root the trace loop takes for a segment's length (geodesic.hip
+ * seg_len) of n DEVICE arguments x; d_out[i] = the root. Returns 0 or a hipError_t value;
+ * asynchronous on hip_stream. */
+int bhrt_check_seg_len(const double* x, int n, double* out, void* hip_stream);
+
 /* Copy and optionally reset this thread's statistics (waits for the timed launches, then reads
  * their counters with a synchronous copy on the legacy default stream, i.e. also after the
  * caller's default-stream work). out == NULL with reset != 0 drops the pending launches'

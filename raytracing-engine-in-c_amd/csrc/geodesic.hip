@@ -447,12 +447,12 @@ __device__ __forceinline__ double rkf45_sum5(double k1, double k3, double k4, do
 // rk4_integrate (math_util.c:162-207) on the six live components; the running sum
 // ((k1 + 2k2) + 2k3) + k4 is the reference's left-to-right evaluation order.
 template <bool SPIN0, bool FAR, bool HUGE, bool HS = false>
-__device__ __forceinline__ void rk4_step(double (&y)[6], double h, const Scene& sc, bool far_ok,
-                                         Counters& n, Trig1& tr, const double* zs = nullptr) {
+__device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, const Scene& sc,
+                                         bool far_ok, Counters& n, Trig1& tr,
+                                         const double* zs = nullptr) {
     constexpr bool Z = zero_accel<SPIN0, FAR>();
     double k[6], acc[6], yt[6];
     const double hh = 0.5 * h;
-    const double h6 = h * (1.0 / 6.0);
     rhs<SPIN0, FAR, HUGE>(y, k, sc, far_ok, n, tr, true);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
@@ -474,8 +474,8 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, const Scene& 
     rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
-        // h * (...) / 6 as (h * RN(1/6)) * (...): the increment differs by <= 1 ulp of itself,
-        // which is ~h*|k| / |y| ulp of the state
+        // h * (...) / 6 as (h * RN(1/6)) * (...), h6 = h * RN(1/6) (the caller's): the increment
+        // differs by <= 1 ulp of itself, which is ~h*|k| / |y| ulp of the state
         if (HS && i < 3)
             y[i] = __builtin_fma(h6, zs[i], y[i]);
         else if (!(Z && i >= 3))
@@ -677,12 +677,31 @@ __device__ __forceinline__ double sqrt_nr(double x) {
     return s;
 }
 
+// sqrt_nr with ONE residual correction: v_rsq_f64 is good to ~2^-24, the
+// Goldschmidt step squares that, and one s += (x - s^2) * hy leaves an error far below the final
+// rounding, so only an argument whose root lies next to a rounding midpoint can come out one
+// ulp off: <= 1 ulp, measured 0 ulp from sqrt on 1e5 arguments over [2^-700, 2^600]
+// (tests/test_gpu_loop_tail.py). Two VALU fewer, and two links off the iteration's dependent
+// chain.
+__device__ __forceinline__ double sqrt_nr1(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    double s = x * y, hy = y * 0.5;
+    const double r = __builtin_fma(-hy, s, 0.5);
+    s = __builtin_fma(s, r, s);
+    hy = __builtin_fma(hy, r, hy);
+    const double e = __builtin_fma(-s, s, x);
+    s = __builtin_fma(e, hy, s);
+    if (__builtin_expect(!(x >= 0x1p-767), 0)) s = sqrt(x);
+    return s;
+}
+
 __device__ __forceinline__ double len3(double x, double y, double z) {
     return sqrt((x * x + y * y) + z * z);  // vector3D_length (math_util.c:85-113)
 }
-// the per-iteration path length |p - p_prev| of the hot loop
+// the per-iteration path length |p - p_prev| of the hot loop: it only feeds the running
+// distance (a sum of up to max_steps of them, compared with max_dist)
 __device__ __forceinline__ double seg_len(double x, double y, double z) {
-    return sqrt_nr((x * x + y * y) + z * z);
+    return sqrt_nr1((x * x + y * y) + z * z);
 }
 
 struct Ray_ {
@@ -696,6 +715,7 @@ struct Ray_ {
     double cd_sd, cd_cm1;        // rotation_trig: sin(delta) and cos(delta) - 1 of the
                                  // increment at the step size h (set with it, hcache)
     double h, h_lo, h_hi;        // hcache: the step size and the r interval it holds on
+    double h6;                   // h * RN(1/6), kept with h where h6cache() (RK4's final update)
     int k;              // iterations executed
     bool far_ok;        // use_analytic_approx && impact_parameter > 0
 };
@@ -873,20 +893,51 @@ __device__ __forceinline__ void ray_init_shared(Ray_& R, const bhrt_camera_k& cm
 }
 
 // check_disk_intersection (raytracer.c:159-196), plane "normal" = previous path point n,
-// straight-line: every lane forms t, the candidate point and the radial test, and the four
+// straight-line. The radial test compares s = qx^2 + qy^2 against the host's thresholds instead
+// of taking sqrt(s) (scene.c sqrt_lower/upper_bound).
+// Every iteration only SCREENS its segment, without a quotient (disk_cand):
+// with t = num / den, den * q = p den + d num, so S = (px den + dx num)^2 + (py den + dy num)^2
+// = s den^2 is compared with the thresholds times den^2, and t < 0 is num den < 0. The four
 // rejections are ONE mask (a per-test early return became nested exec-mask regions, ~50 SALU
-// per iteration). The radial test compares s = qx^2 + qy^2 against the host's thresholds
-// instead of taking sqrt(s) (scene.c sqrt_lower/upper_bound). t = num * RN(1/den) for
-// |den| in [1e-10, 1e150) (a lane whose |den| < 1e-10 is rejected whatever its t); the IEEE
-// quotient, in a rare branch, otherwise (NaN den included). A t < 0 by signs (|num| > 0) is
-// negative here too, so the reference's rejection order is kept without a sign test.
-__device__ __forceinline__ bool disk_hit(const Ray_& R, double nx, double ny, double nz,
-                                         const Scene& sc, double big, double& qx, double& qy,
-                                         double& qz) {
-    const double den = (R.dx * nx + R.dy * ny) + R.dz * nz;
-    const double num = -((R.px * nx + R.py * ny) + R.pz * nz);
-    double t = div_nr(num, den, rcp_nr(den));
-    if (__builtin_expect(!(fabs(den) < big), 0)) t = num / den;  // big = 1e150
+// per iteration). A lane that passes the screen -- about once per hitting ray -- then makes the
+// reference's decision literally, in a rare branch (disk_decide): |den| < 1e-10, t by the IEEE
+// quotient, t < 0, the point, s against the thresholds. So a hit is always one the literal form
+// accepts, and the screen only has to pass every lane the literal form could accept:
+//   - |den| >= big (2^100), a NaN or Inf den included, passes unscreened: below it den^2, the
+//     scaled thresholds and S stay finite for points and directions below 2^100 and radii
+//     below 2^400 (far beyond them an S that overflows to Inf fails the outer comparison
+//     unless that threshold is Inf too);
+//   - the sign test rejects only den (num + 2^-1000 den) < 0, i.e. t < -2^-1000, where
+//     RN(num / den) is a negative normal. A t that is or rounds to -0.0 (num = +-0, or an
+//     underflowed quotient), which the reference accepts, is never rejected; nor is a product
+//     that underflows to -0;
+//   - |den| < 1e-10 is left to the literal form;
+//   - S carries two roundings per component where the reference's s carries those of t, d t
+//     and p + d t: the screen and the literal form can only disagree for a candidate point
+//     within a few ulp of a rim, where the screen may reject a point the reference accepts
+//     by that margin (never the other way round).
+// A NaN operand fails the screen's comparisons as it fails the reference's. Radii whose
+// squares times den^2 would be subnormal (below ~1e-144) are screened at the subnormals'
+// precision.
+__device__ __forceinline__ bool disk_cand(const Ray_& R, double nx, double ny, double nz,
+                                          const Scene& sc, double big, double& num,
+                                          double& den) {
+    den = (R.dx * nx + R.dy * ny) + R.dz * nz;
+    num = -((R.px * nx + R.py * ny) + R.pz * nz);
+    const double d2 = den * den;
+    const double sg = den * __builtin_fma(0x1p-1000, den, num);
+    const double sx = __builtin_fma(R.dx, num, R.px * den);
+    const double sy = __builtin_fma(R.dy, num, R.py * den);
+    const double S = sx * sx + sy * sy;
+    return (!(sg < 0.0) & (S >= sc.disk_in_sq * d2) & (S <= sc.disk_out_sq * d2)) |
+           !(fabs(den) < big);
+}
+
+// The reference's decision for a lane that passed the screen, and its candidate point
+__device__ __forceinline__ bool disk_decide(const Ray_& R, double num, double den,
+                                            const Scene& sc, double& qx, double& qy,
+                                            double& qz) {
+    const double t = num / den;
     qx = R.px + R.dx * t;
     qy = R.py + R.dy * t;
     qz = R.pz + R.dz * t;
@@ -894,12 +945,21 @@ __device__ __forceinline__ bool disk_hit(const Ray_& R, double nx, double ny, do
     return !(fabs(den) < kEps) & !(t < 0.0) & (s >= sc.disk_in_sq) & (s <= sc.disk_out_sq);
 }
 
+__device__ __forceinline__ bool disk_hit(const Ray_& R, double nx, double ny, double nz,
+                                         const Scene& sc, double big, double& qx, double& qy,
+                                         double& qz) {
+    double num, den;
+    return disk_cand(R, nx, ny, nz, sc, big, num, den) &&
+           disk_decide(R, num, den, sc, qx, qy, qz);
+}
+
 enum Term : int { T_NONE = 0, T_HORIZON, T_DISK, T_MAXDIST, T_MAXSTEPS };
 
 struct HSel {  // the four step sizes of the schedule, hoisted out of the kernel argument block
     double far_, r15, r5, r2_5;
-    double big;  // 1e150, the disk test's quotient bound: an SGPR pair set once, outside the
-                 // loop (as a literal it was rematerialised by two s_mov in every iteration)
+    double big;  // 2^100, the disk test's bound on |den| (disk_hit): an SGPR pair set once,
+                 // outside the loop (as a literal it was rematerialised by two s_mov in every
+                 // iteration)
 };
 
 // x unchanged, but opaque to the optimiser: the four step sizes stay four register values
@@ -919,7 +979,7 @@ __device__ __forceinline__ double opaque(double x) {
 template <bool V = false>
 __device__ __forceinline__ HSel hsel_of(const Scene& sc) {
     return HSel{opaque<V>(sc.h_far), opaque<V>(sc.h_15), opaque<V>(sc.h_5), opaque<V>(sc.h_2_5),
-                opaque<false>(1.0e150)};
+                opaque<false>(0x1p100)};
 }
 
 // :543-548, state NaN/Inf recovery at the top of an iteration. One test of the sum
@@ -957,6 +1017,17 @@ constexpr bool hcache() {
            rotation_trig<METHOD, SPIN0, FAR, HUGE>();
 }
 
+// Where RK4's h * RN(1/6) is kept beside the cached step size and set with it, in the same rare
+// branch: the zero-acceleration RK4 path (C4), whose ~60-VALU iteration otherwise re-forms the
+// product -- a v_mov_b64 of the constant, an s_nop and the v_mul_f64 -- every time. The same
+// product of the same operands, so bit-identical. It costs two more loop-carried registers, so
+// it is kept to the path whose listing shows the product: the a = 0 iterations (C1, C2: ~300
+// VALU each) keep the inline form.
+template <int METHOD, bool SPIN0, bool FAR, bool HUGE>
+constexpr bool h6cache() {
+    return METHOD == INTEGRATOR_RK4 && rotation_trig<METHOD, SPIN0, FAR, HUGE>();
+}
+
 // One pass of integrate_photon_path's loop body (raytracer.c:517-665) plus, with DISK, the
 // on-the-fly form of trace_ray's segment scan. Returns the termination, or T_NONE.
 // hs: the step sizes in registers (k_trace), or NULL to read them from the scene.
@@ -970,7 +1041,7 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
     // step schedule (:556-571), written as selects so the first true test wins; fmin(h, 0.1)
     // is folded into the values (host)
     const double r = R.y[1];
-    double h;
+    double h, h6 = 0.0;
     if constexpr (hcache<METHOD, SPIN0, FAR, HUGE>()) {
         // the size is cached per ray with the r interval it holds on (Scene h_lo / h_hi): a ray
         // changes regime at most three times, so each iteration is two compares instead of the
@@ -999,19 +1070,26 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
                     double a = R.y[5];
                     a = rk4_acc(a, R.y[5]);
                     a = rk4_acc(a, R.y[5]);
-                    d = (R.h * (1.0 / 6.0)) * (a + R.y[5]);
+                    R.h6 = R.h * (1.0 / 6.0);
+                    d = R.h6 * (a + R.y[5]);
                 } else {
                     d = R.h * R.zs[5];
                 }
                 rotation_coeffs(d, R.cd_sd, R.cd_cm1);
             }
         }
-        h = R.h;
         // h formed at the branch's join: left visible, the compiler sank the step's first uses
         // of h into both arms, and the rare re-select became an if/else diamond (s_xor +
         // s_andn2_saveexec per iteration). C4 SALU 145 -> 137 M per launch, C5 +2%,
         // bit-identical (profiles/r04/session_ad)
-        asm volatile("" : "+v"(h));
+        // (the barrier on the carried value itself: on a copy of it, it cost a v_mov_b64 and an
+        // s_nop in every iteration)
+        asm volatile("" : "+v"(R.h));
+        h = R.h;
+        if constexpr (h6cache<METHOD, SPIN0, FAR, HUGE>()) {
+            asm volatile("" : "+v"(R.h6));
+            h6 = R.h6;
+        }
     } else {
         h = hs.far_;
         h = (r < sc.rs_x15) ? hs.r15 : h;
@@ -1024,7 +1102,8 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
     const double a2 = R.y[2], a3 = R.y[3];
     constexpr bool HS = hoist_sums<METHOD, SPIN0, FAR, HUGE>();
     if (METHOD == INTEGRATOR_RK4) {
-        rk4_step<SPIN0, FAR, HUGE, HS>(R.y, h, sc, R.far_ok, n, tr, R.zs);
+        if (!h6cache<METHOD, SPIN0, FAR, HUGE>()) h6 = h * (1.0 / 6.0);
+        rk4_step<SPIN0, FAR, HUGE, HS>(R.y, h, h6, sc, R.far_ok, n, tr, R.zs);
     } else if (METHOD == INTEGRATOR_RKF45) {
         moved = rkf45_attempt<SPIN0, FAR, HUGE, HS, ACC>(R.y, h, sc, R.far_ok, n, tr, R.zs);
     } else {
@@ -1075,15 +1154,18 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
         term = (R.dist >= sc.max_dist) ? T_MAXDIST : term;
         term = (R.y[1] <= sc.rs_x1_05) ? T_HORIZON : term;
         // segment k = (p_k, p_{k-1}) is stored and scanned by trace_ray iff k < max_steps
-        double qx, qy, qz;
-        if (disk_hit(R, ox, oy, oz, sc, hs.big, qx, qy, qz) & (R.k < sc.max_steps)) {
-            // the ray ends here: the hit point replaces the current point, so no extra
-            // loop-carried registers hold it (store_hit reads it from R.px..pz; +0.9% on C2)
-            R.px = qx;
-            R.py = qy;
-            R.pz = qz;
-            R.dist += seg_len(qx - ox, qy - oy, qz - oz);  // (= len3: sqrt_nr is sqrt here)
-            term = T_DISK;
+        double qx, qy, qz, num, den;
+        if (disk_cand(R, ox, oy, oz, sc, hs.big, num, den) & (R.k < sc.max_steps)) {
+            if (disk_decide(R, num, den, sc, qx, qy, qz)) {
+                // the ray ends here: the hit point replaces the current point, so no extra
+                // loop-carried registers hold it (store_hit reads it from R.px..pz; +0.9% on C2)
+                R.px = qx;
+                R.py = qy;
+                R.pz = qz;
+                const double ux = qx - ox, uy = qy - oy, uz = qz - oz;
+                R.dist += sqrt_nr((ux * ux + uy * uy) + uz * uz);  // (= len3: sqrt_nr is sqrt here)
+                term = T_DISK;
+            }
         }
         if (!moved && term == T_NONE) {
             // Fixed point: every later iteration repeats this one with p_j = p_{j-1} = p_k.
@@ -2388,6 +2470,36 @@ __global__ void k_check_accept(const double* err, const double* scale, const dou
     out[2 * i + 1] = rkf45_accept<false>(e, s, tol[i]);
 }
 
+// The trace loop's disk decision (disk_hit) on given operands: case i is the point p[3i..3i+2],
+// the direction d[3i..] and the "normal" n[3i..] (the previous path point); out[i] = the
+// decision against the thresholds in_sq, out_sq (Scene disk_in_sq / disk_out_sq). One wave per
+// workgroup, so lanes of either form share a wave as they do in the loop.
+__global__ void k_check_disk_hit(const double* p, const double* d, const double* nrm, int n,
+                                 double in_sq, double out_sq, int* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Scene sc{};
+    sc.disk_in_sq = in_sq;
+    sc.disk_out_sq = out_sq;
+    Ray_ R{};
+    R.px = p[3 * i];
+    R.py = p[3 * i + 1];
+    R.pz = p[3 * i + 2];
+    R.dx = d[3 * i];
+    R.dy = d[3 * i + 1];
+    R.dz = d[3 * i + 2];
+    const HSel hs = hsel_of(sc);
+    double qx, qy, qz;
+    out[i] = disk_hit(R, nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], sc, hs.big, qx, qy, qz);
+}
+
+// The root seg_len takes of its sum (sqrt_nr1) on given arguments
+__global__ void k_check_seg_len(const double* x, int n, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = sqrt_nr1(x[i]);
+}
+
 // ---- launch plumbing --------------------------------------------------------------------
 // Launch geometry is cached per device: a process may drive several devices (bhrt_render_frame
 // splits a frame over every visible one) from several host threads. Every cached value is a
@@ -2667,6 +2779,23 @@ extern "C" __attribute__((visibility("default"))) int bhrt_check_rkf45_accept(
     if (n <= 0) return 0;
     k_check_accept<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(
         d_err, d_scale, d_tol, n, d_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default"))) int bhrt_check_disk_hit(
+    const double* d_p, const double* d_d, const double* d_n, int n, double in_sq, double out_sq,
+    int* d_out, void* stream) {
+    if (n <= 0) return 0;
+    k_check_disk_hit<<<(n + 63) / 64, 64, 0, static_cast<hipStream_t>(stream)>>>(
+        d_p, d_d, d_n, n, in_sq, out_sq, d_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default"))) int bhrt_check_seg_len(const double* d_x, int n,
+                                                                         double* d_out,
+                                                                         void* stream) {
+    if (n <= 0) return 0;
+    k_check_seg_len<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_x, n, d_out);
     return (int)hipGetLastError();
 }
 
