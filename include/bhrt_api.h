@@ -645,6 +645,14 @@ int bhrt_check_disk_hit(const double* p, const double* d, const double* nrm, int
  * asynchronous on hip_stream. */
 int bhrt_check_seg_len(const double* x, int n, double* out, void* hip_stream);
 
+/* Diagnostic: the reciprocal two RK4 a = 0 stages share (geodesic.hip pair_rcp) on n cases of a
+ * DEVICE array in[4n] = (rc_a, st_a, rc_b, st_b), the stages' clamped r and sin theta;
+ * d_out[5i..5i+3] = 1 / rc_a, 1 / st_a, 1 / rc_b, 1 / st_b as the stages form them, d_out[5i+4]
+ * = 1.0 where the pair's range test passes (0.0: both stages take the literal form, not these).
+ * huge != 0: with the rc < 1e150 test of the redo pass. Returns 0 or a hipError_t value;
+ * asynchronous on hip_stream. */
+int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hip_stream);
+
 /* Copy and optionally reset this thread's statistics (waits for the timed launches, then reads
  * their counters with a synchronous copy on the legacy default stream, i.e. also after the
  * caller's default-stream work). out == NULL with reset != 0 drops the pending launches'

@@ -49,6 +49,7 @@ typedef struct {
                         rotation_trig); a ray at or above it is re-traced by the redo pass */
     int accept_all;  /* RKF45 with 2^-30 <= tol <= 2^300 and finite step sizes: no attempt on the
                         zero-acceleration paths can be rejected (geodesic.hip rkf45_attempt ACC) */
+    double m_4;      /* M / 4: the a = 0 stage forms -M / r^2 from -2 / r (geodesic.hip rhs) */
 } bhrt_scene_k;
 
 typedef struct {

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "bhrt_kernel.h"
 
@@ -45,9 +46,23 @@ constexpr double kTwoPi = 6.28318530717958647692;
 
 using Scene = bhrt_scene_k;
 
+// The mark ray_iterate<MASK> (k_trace's wave-uniform trip) puts on a ray's step count when the
+// ray must leave the trip for a reason that is no compare of its own: a disk hit, or `huge`
+// (ORed in from Counters::mark). The trip's guard then sees it in the step-budget compare
+// (unsigned) instead of balloting two more lane masks.
+constexpr int kStopMark = (int)0x80000000u;
 struct Counters {
     unsigned rays = 0, iters = 0, full = 0, far_ = 0, kerr = 0;
     bool huge = false;  // a sincos argument needed the large-argument path (see bhrt_sincos)
+    int mark = 0;       // kStopMark while `huge` is raised
+    __device__ __forceinline__ void raise_huge() {
+        huge = true;
+        mark = kStopMark;
+    }
+    __device__ __forceinline__ void clear_huge() {
+        huge = false;
+        mark = 0;
+    }
 };
 
 // Division without the generic fdiv scaffolding.
@@ -65,6 +80,16 @@ __device__ __forceinline__ double rcp_nr(double b) {
     return __builtin_fma(y, __builtin_fma(e, e, e), y);
 }
 __device__ __forceinline__ double div_nr(double a, double /*b*/, double yb) { return a * yb; }
+// -2 * rcp_nr(b), bit for bit: the seed is scaled by -2 (a power of two, exact) beside the
+// residual, and the same refinement runs on the scaled seed, so every intermediate is rcp_nr's
+// times -2 (b in the normal range, as for rcp_nr). One product off the dependent chain instead
+// of the two `* -2.0` of rhs's accelerations behind it.
+__device__ __forceinline__ double rcp_nr_m2(double b) {
+    const double y = __builtin_amdgcn_rcp(b);
+    const double e = __builtin_fma(-b, y, 1.0);
+    const double y2 = y * -2.0;
+    return __builtin_fma(y2, __builtin_fma(e, e, e), y2);
+}
 
 // fma(a, b, c) with c a compile-time coefficient, as ONE v_fma_f64 whose addend is an SGPR
 // pair (set up by SALU). Left to itself hipcc copies the coefficient into the destination
@@ -112,7 +137,7 @@ __device__ __forceinline__ void bhrt_sincos(double x, double* so, double* co,
             sincos_ocml(x, so, co);
             return;
         }
-        if (fabs(x) <= 1.79769313486231570815e+308) hc->huge = true;
+        if (fabs(x) <= 1.79769313486231570815e+308) hc->raise_huge();
     }
     constexpr double kTwoOverPi = 6.36619772367581382433e-01;
     constexpr double P1 = 1.57079632679489655800e+00;   // pi/2 in three parts
@@ -285,6 +310,34 @@ __device__ __forceinline__ void repair_clamp(double (&d)[6]) {
     for (int i = 3; i < 6; i++) d[i] = fmin(fmax(d[i], -10.0), 10.0);
 }
 
+// The a = 0 accelerations of one stage in the fast form, given w2 = -2 / (rc st) (rhs, which
+// takes it from the stage's own reciprocal, or rk4_step's pair, which shares one between two
+// stages). ok: the operands the reciprocal was taken of are in range -- |sin theta| >= 0.01 and,
+// where it is tested, rc < 1e150, of this stage and of the one it shares the reciprocal with.
+// A lane that fails it, or whose result is not a plain |d| <= 10 value, recomputes the stage in
+// the literal form (its own reciprocals) before the repair and clamps.
+template <bool HUGE>
+__device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6], const Scene& sc,
+                                           double st, double ct, double rc, double w2, bool ok) {
+    // The factor -2 of d4 and d5 rides on the reciprocal (w2 = -2 / (r sin theta), rcp_nr_m2):
+    // yr2 = -2 / r, ys2 = -2 / sin theta and p2 = -2 v_r / r are the former yr, ys, p times a
+    // power of two, so every product and FMA below rounds as before -- d4 = fma(p * -2, v_th,
+    // ..), d5 = (v_ph * -2) * fma(v_th, cos th * ys, p), d3 = fma(-(M yr), yr, f3) with
+    // (M / 4 * yr2) * yr2, M / 4 the host's (Scene m_4) -- bit-identical, one VALU less
+    const double yr2 = st * w2, ys2 = rc * w2;
+    const double u = st * y[5];
+    const double f3 = rc * __builtin_fma(u, u, y[4] * y[4]);
+    d[3] = __builtin_fma(-(sc.m_4 * yr2), yr2, f3);
+    const double p2 = y[3] * yr2;
+    d[4] = __builtin_fma(p2, y[4], u * (ct * y[5]));
+    d[5] = y[5] * __builtin_fma(y[4], ct * ys2, p2);
+    const int plain = (int)ok & (int)(fabs(d[3]) <= 10.0) & (int)(fabs(d[4]) <= 10.0) &
+                      (int)(fabs(d[5]) <= 10.0);
+    if (__builtin_expect(plain, 1)) return;
+    accel_literal(y, d, sc, st, ct);
+    repair_clamp<!HUGE>(d);
+}
+
 // ray_derivatives (raytracer.c:44-154) for one RK stage. y = (t, r, theta, phi, tdot, rdot)
 // of the caller, read -- as the reference does -- as (r, theta, phi, v_r, v_theta, v_phi).
 // Stage counters: FAR instantiations count their far-field stages (a lane's branch varies);
@@ -333,24 +386,12 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
         const double rc = max_raw(y[0], sc.rs_x1_5);
         // 1/r and 1/sin theta from one reciprocal of the product (r sin theta in [0.03, 1e150]):
         // one v_rcp_f64 + refinement fewer per stage, <= ~2 ulp instead of 1 (+1.7% at 4 waves)
-        const double w = rcp_nr(rc * st);
-        const double yr = st * w, ys = rc * w;
-        const double u = st * y[5];
-        const double f3 = rc * __builtin_fma(u, u, y[4] * y[4]);
-        d[3] = __builtin_fma(-(sc.M * yr), yr, f3);
-        const double p = y[3] * yr;
-        d[4] = __builtin_fma(p * -2.0, y[4], u * (ct * y[5]));
-        d[5] = (y[5] * -2.0) * __builtin_fma(y[4], ct * ys, p);
         // rc < 1e150 (every divisor of the literal form normal) needs no test in k_trace's hot
         // instantiations: state[0] starts at t = 0 there and moves by h * state[3], whose own
         // derivative is the clamped |d3| <= 10 (or 0), so |state[0]| <= 0.1 * 20 * steps^2;
         // k_path (a caller-given t) and the HUGE redo keep it
-        const int plain = (int)(!HUGE ? true : rc < 1.0e150) & (int)(fabs(d[3]) <= 10.0) &
-                          (int)(fabs(d[4]) <= 10.0) & (int)(fabs(d[5]) <= 10.0) &
-                          (int)(fabs(st) >= 0.01);
-        if (__builtin_expect(plain, 1)) return;
-        accel_literal(y, d, sc, st, ct);
-        repair_clamp<!HUGE>(d);
+        const bool ok = (!HUGE ? true : rc < 1.0e150) & (fabs(st) >= 0.01);
+        accel_fast<HUGE>(y, d, sc, st, ct, rc, rcp_nr_m2(rc * st), ok);
         return;
     }
     // :131-138
@@ -444,6 +485,71 @@ __device__ __forceinline__ double rkf45_sum5(double k1, double k3, double k4, do
     return kD1 * k1 + kD3 * k3 + kD4 * k4 + kD5 * k5 + kD6 * k6;
 }
 
+// One reciprocal for two a = 0 stages. In RK4 the position part of
+// stage 3's state is y + h/2 * (stage 2's velocities), and those are part of stage 2's STATE,
+// known before stage 2's accelerations are: both stages' x = rc sin theta exist right after
+// stage 1, and w = -2 / (x_a x_b) gives -2 / x_a = x_b w and -2 / x_b = x_a w: one v_rcp_f64 and
+// its refinement (7 issue slots) less for three products. Against the single form's
+// yr = st RN(1 / RN(rc st)) a member's yr = st RN(x_b RN(1 / RN(x_a x_b))) carries one rounding
+// more (x_b's own rounding cancels): five roundings, <= 6 ulp of 1 / rc with the reciprocal's
+// own taken as <= 1 ulp (measured worst: profiles/stagepairs/test_figures.txt).
+// A member of the far-field branch has no reciprocal to share: it contributes x = 1.
+// ok: BOTH members' operands in range (|sin theta| >= 0.01, and rc < 1e150 where that is
+// tested): then P = x_a x_b lies in [(0.015 rs)^2, 1e300], normal, and so is w. A member whose
+// sin theta is 0, subnormal or NaN -- which would poison or coarsen the shared w -- fails it FOR
+// BOTH, and both stages take the literal form with their own reciprocals (accel_fast): a stage
+// never uses a quotient derived from an out-of-range partner. (An Inf, which no sine is, passes
+// the test and turns both members' quotients into NaN, which fail the plain-value test.)
+#ifndef BHRT_PAIR_RCP /* 1: RK4 a = 0 stages 2 and 3 share a reciprocal; 0: each its own */
+#define BHRT_PAIR_RCP 1
+#endif
+struct StageOps {
+    double st, ct, rc, x;  // sin, cos of the stage's theta, its clamped r, x = rc * st (far: 1)
+    bool ok;
+};
+template <bool HUGE>
+__device__ __forceinline__ void stage_x(StageOps& o) {  // x and the range test from st, rc
+    o.x = o.rc * o.st;
+    o.ok = (!HUGE ? true : o.rc < 1.0e150) & (fabs(o.st) >= 0.01);
+}
+template <bool FAR, bool HUGE>
+__device__ __forceinline__ void stage_ops(double y0, double y1, bool far, const Scene& sc,
+                                          Counters& n, const Trig1& tr, StageOps& o) {
+    shift_or_eval(tr.a, tr.s, tr.c, y1, o.st, o.ct, HUGE ? nullptr : &n);
+    o.rc = max_raw(y0, sc.rs_x1_5);
+    stage_x<HUGE>(o);
+    if (FAR && far) {
+        o.x = 1.0;
+        o.ok = true;
+    }
+}
+// wa = -2 / a.x, wb = -2 / b.x from one reciprocal; false: a member is out of range (above)
+__device__ __forceinline__ bool pair_rcp(const StageOps& a, const StageOps& b, double& wa,
+                                         double& wb) {
+    const double w = rcp_nr_m2(a.x * b.x);
+    wa = b.x * w;
+    wb = a.x * w;
+    return a.ok & b.ok;
+}
+// rhs for a stage whose operands and reciprocal are given (stage_ops, pair_rcp)
+template <bool FAR, bool HUGE>
+__device__ __forceinline__ void rhs_given(const double (&y)[6], double (&d)[6], const Scene& sc,
+                                          bool far, Counters& n, const StageOps& o, double w2,
+                                          bool ok) {
+    d[0] = y[3];
+    d[1] = y[4];
+    d[2] = y[5];
+    if (FAR && far) {  // weak-field branch, as in rhs
+        d[3] = 0.0;
+        d[4] = 0.0;
+        d[5] = y[5] * (sc.two_m / (y[0] * y[0]));
+        n.far_++;
+        return;
+    }
+    if ((FAR && HUGE) || BHRT_COUNT_STAGES) n.full++;
+    accel_fast<HUGE>(y, d, sc, o.st, o.ct, o.rc, w2, ok);
+}
+
 // rk4_integrate (math_util.c:162-207) on the six live components; the running sum
 // ((k1 + 2k2) + 2k3) + k4 is the reference's left-to-right evaluation order.
 template <bool SPIN0, bool FAR, bool HUGE, bool HS = false>
@@ -459,13 +565,36 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         acc[i] = k[i];
         yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
     }
-    rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
+    if constexpr (SPIN0 && BHRT_PAIR_RCP) {
+        // stages 2 and 3 on one reciprocal (pair_rcp). Stage 3's y0, y1 are the very expressions
+        // the stage-state loop below would form (k[0..1] of stage 2 are yt[3..4]).
+        const double y30 = y[0] + hh * yt[3], y31 = y[1] + hh * yt[4];
+        const bool far2 = FAR && far_ok && yt[0] > sc.rs_x15;
+        const bool far3 = FAR && far_ok && y30 > sc.rs_x15;
+        StageOps o2, o3;
+        double w2 = 0.0, w3 = 0.0;
+        bool ok = false;
+        if (!FAR || !(far2 & far3)) {
+            stage_ops<FAR, HUGE>(yt[0], yt[1], far2, sc, n, tr, o2);
+            stage_ops<FAR, HUGE>(y30, y31, far3, sc, n, tr, o3);
+            ok = pair_rcp(o2, o3, w2, w3);
+        }
+        rhs_given<FAR, HUGE>(yt, k, sc, far2, n, o2, w2, ok);
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        acc[i] = rk4_acc(acc[i], k[i]);
-        yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
+        for (int i = 0; i < 6; i++) {
+            acc[i] = rk4_acc(acc[i], k[i]);
+            yt[i] = i == 0 ? y30 : i == 1 ? y31 : y[i] + hh * k[i];
+        }
+        rhs_given<FAR, HUGE>(yt, k, sc, far3, n, o3, w3, ok);
+    } else {
+        rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            acc[i] = rk4_acc(acc[i], k[i]);
+            yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
+        }
+        rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
     }
-    rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
         acc[i] = rk4_acc(acc[i], k[i]);
@@ -1031,9 +1160,16 @@ constexpr bool h6cache() {
 // One pass of integrate_photon_path's loop body (raytracer.c:517-665) plus, with DISK, the
 // on-the-fly form of trace_ray's segment scan. Returns the termination, or T_NONE.
 // hs: the step sizes in registers (k_trace), or NULL to read them from the scene.
-template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, bool ACC = false>
-__device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n,
-                                           const HSel hs) {
+// MASK (k_trace's wave-uniform trip, exit_masks): the return value is the WAVE's mask of lanes
+// whose ray ends here -- the exit compares, each its own ballot, ORed as scalars -- and a disk
+// hit is noted in the sign bit of R.k, where the step-budget compare (unsigned) sees it; the
+// caller forms the termination on the trip's exit edge (exit_term). The iteration itself is the
+// same arithmetic either way.
+template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, bool ACC = false,
+          bool MASK = false>
+__device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray_iterate(
+    Ray_& R, const Scene& sc, Counters& n, const HSel hs) {
+    static_assert(!MASK || (DISK && METHOD == INTEGRATOR_RK4), "MASK: every iteration moves");
     Counters* const hc = HUGE ? nullptr : &n;
     // Instantiations with repair_at_refill() run the recovery once, when the ray is loaded:
     // there a finite state stays finite.
@@ -1150,13 +1286,21 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
         // step budget; a disk hit overrides the others below)
         // (as three selects, lowest priority first: the nested form compiled to exec-mask
         // branches)
-        int term = (R.k >= sc.max_steps) ? T_MAXSTEPS : T_NONE;
-        term = (R.dist >= sc.max_dist) ? T_MAXDIST : term;
-        term = (R.y[1] <= sc.rs_x1_05) ? T_HORIZON : term;
+        int term = T_NONE;
+        if constexpr (!MASK) {
+            term = (R.k >= sc.max_steps) ? T_MAXSTEPS : T_NONE;
+            term = (R.dist >= sc.max_dist) ? T_MAXDIST : term;
+            term = (R.y[1] <= sc.rs_x1_05) ? T_HORIZON : term;
+        }
         // segment k = (p_k, p_{k-1}) is stored and scanned by trace_ray iff k < max_steps
+        // (MASK: that test inside the candidates' rare branch -- beside k >= max_steps above it
+        // was a second compare of the same operands in every iteration; the barrier keeps the
+        // compiler from hoisting it back)
         double qx, qy, qz, num, den;
-        if (disk_cand(R, ox, oy, oz, sc, hs.big, num, den) & (R.k < sc.max_steps)) {
-            if (disk_decide(R, num, den, sc, qx, qy, qz)) {
+        if (disk_cand(R, ox, oy, oz, sc, hs.big, num, den) & (MASK || R.k < sc.max_steps)) {
+            int kq = R.k;
+            if constexpr (MASK) asm volatile("" : "+v"(kq));
+            if ((!MASK || kq < sc.max_steps) && disk_decide(R, num, den, sc, qx, qy, qz)) {
                 // the ray ends here: the hit point replaces the current point, so no extra
                 // loop-carried registers hold it (store_hit reads it from R.px..pz; +0.9% on C2)
                 R.px = qx;
@@ -1165,7 +1309,18 @@ __device__ __forceinline__ int ray_iterate(Ray_& R, const Scene& sc, Counters& n
                 const double ux = qx - ox, uy = qy - oy, uz = qz - oz;
                 R.dist += sqrt_nr((ux * ux + uy * uy) + uz * uz);  // (= len3: sqrt_nr is sqrt here)
                 term = T_DISK;
+                if constexpr (MASK) R.k |= kStopMark;
             }
+        }
+        if constexpr (MASK) {
+            // a v_cmp's result IS the ballot of its lanes: three compares and two scalar ORs, no
+            // 32-bit select and no compare of a code (the ballot of an ORed lane mask came out
+            // as a v_cndmask and a v_cmp). 0 < max_steps here, so the unsigned compare is the
+            // budget test for a step count and true for one that carries kStopMark.
+            R.k |= n.mark;  // (`huge` raised: Counters)
+            return __builtin_amdgcn_ballot_w64((unsigned)R.k >= (unsigned)sc.max_steps) |
+                   __builtin_amdgcn_ballot_w64(R.dist >= sc.max_dist) |
+                   __builtin_amdgcn_ballot_w64(R.y[1] <= sc.rs_x1_05);
         }
         if (!moved && term == T_NONE) {
             // Fixed point: every later iteration repeats this one with p_j = p_{j-1} = p_k.
@@ -1617,6 +1772,30 @@ constexpr bool uniform_trip() {
     return BHRT_UNIFORM_TRIP == 1 ||
            (BHRT_UNIFORM_TRIP == 2 && METHOD == INTEGRATOR_RK4 && SPIN0);
 }
+// The exits of a wave-uniform trip as lane masks (ray_iterate MASK): the trip's guard needs only
+// "does any lane stop", so an iteration ORs the ballots of its three exit compares (SALU; a disk
+// hit and a `huge` ray are marked on the step count, kStopMark, and show in the budget compare);
+// the termination code -- three 32-bit selects and a compare of the code in every iteration
+// before -- is formed once, on the edge the trip leaves by (exit_term), from the same compares
+// of the same final values. RK4 disk instantiations only (every iteration moves, so there is no
+// fixed-point exit). The reference's exit order and every output are unchanged.
+#ifndef BHRT_EXIT_MASKS
+#define BHRT_EXIT_MASKS 1
+#endif
+template <int METHOD, bool DISK, bool SPIN0>
+constexpr bool exit_masks() {
+    return BHRT_EXIT_MASKS && uniform_trip<METHOD, SPIN0>() && DISK && METHOD == INTEGRATOR_RK4;
+}
+// the reference's exit order (disk, horizon, distance, step budget) after ray_iterate<MASK>,
+// T_NONE for a lane that goes on; takes the disk hit's mark off the step count
+__device__ __forceinline__ int exit_term(Ray_& R, const Scene& sc) {
+    const bool dhit = R.k < 0;
+    R.k &= ~kStopMark;
+    int term = (R.k >= sc.max_steps) ? T_MAXSTEPS : T_NONE;
+    term = (R.dist >= sc.max_dist) ? T_MAXDIST : term;
+    term = (R.y[1] <= sc.rs_x1_05) ? T_HORIZON : term;
+    return dhit ? T_DISK : term;
+}
 template <int METHOD, bool SPIN0, bool FAR, bool HUGE, bool ACC = false>
 constexpr int unroll_n() {
     return HUGE                      ? 1
@@ -1846,16 +2025,16 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                     // trip's one iteration is discarded; a branch here would cost spills at
                     // every refill)
                     if (FAR && !HUGE && !(kp.sc.far_bounded && state_within(R, 0x1p40)))
-                        n.huge = true;
+                        n.raise_huge();
                     // the rotation of state[2]'s sin, cos needs |h state[5]| < pi/4 (rotation_trig)
                     if (rotation_trig<METHOD, SPIN0, FAR, HUGE>() && !(fabs(R.y[5]) < kp.sc.rot_vmax))
-                        n.huge = true;
+                        n.raise_huge();
                     n.rays++;
                     live = true;
                     if (kp.sc.max_steps <= 0) {  // loop never runs: MAX_STEPS, steps 0
                         store_ray<METHOD, DISK, SPIN0>(kc, rid, R, T_MAXSTEPS);
                         live = false;
-                        n.huge = false;
+                        n.clear_huge();
                     }
                 }
             }
@@ -1874,11 +2053,23 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
         st_trips++;
 #endif
         if (live) {
-            int term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
             // further iterations in the same trip for rays that go on: the loop's hand-over
             // copies between iterations (state, point, distance, carried sin/cos) fold away. A
             // lane's iterations are the same either way; only its refill point moves.
-            if constexpr (uniform_trip<METHOD, SPIN0>()) {
+            int term;
+            if constexpr (exit_masks<METHOD, DISK, SPIN0>()) {
+                // (the wave-uniform guard below, on the wave's exit mask)
+                unsigned long long stop =
+                    ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true>(R, kp.sc, n, hsel);
+#pragma unroll
+                for (int u = 1; u < unroll_n<METHOD, SPIN0, FAR, HUGE, ACC>(); u++) {
+                    if (stop != 0ull) break;  // (a lane that raised `huge` is marked: Counters)
+                    stop = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true>(R, kp.sc, n, hsel);
+                }
+                term = T_NONE;
+                if (stop != 0ull) term = exit_term(R, kp.sc);
+            } else if constexpr (uniform_trip<METHOD, SPIN0>()) {
+                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
                 // wave-uniform guard: the trip goes on only while EVERY live lane does, so the
                 // next iteration runs on the same exec mask -- no per-lane region around it, and
                 // no copies of the values a lane that stopped must keep (they are copied once, on
@@ -1889,6 +2080,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                     term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
                 }
             } else {
+                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
 #pragma unroll
                 for (int u = 1; u < unroll_n<METHOD, SPIN0, FAR, HUGE, ACC>(); u++)
                     if (term == T_NONE && !n.huge)
@@ -1897,7 +2089,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
             if (METHOD == INTEGRATOR_RK4 && (term != T_NONE || (!HUGE && n.huge)))
                 n.iters += R.k;  // every RK4 iteration moves, so R.k = iterations executed
             if (!HUGE && n.huge) {  // hand the ray to the HUGE instantiation
-                n.huge = false;
+                n.clear_huge();
                 n.rays--;
                 kp.redo[atomicAdd(kp.ctl + 6, 1ull)] = rid;
                 // no redo pass follows a launch the host proved eviction-free: if that proof
@@ -2500,6 +2692,36 @@ __global__ void k_check_seg_len(const double* x, int n, double* out) {
     out[i] = sqrt_nr1(x[i]);
 }
 
+// The shared reciprocal of an RK4 stage pair (stage_x, pair_rcp) on given operands: case i is
+// (rc_a, st_a, rc_b, st_b) = in[4i..4i+3]; out[5i..5i+3] = 1 / rc_a, 1 / st_a, 1 / rc_b, 1 / st_b
+// as the stages form them (accel_fast's yr2, ys2 times -1/2, exact) and out[5i+4] = the pair's
+// range test (1: both stages use these quotients; 0: both take the literal form instead).
+// huge: with the rc < 1e150 test of the HUGE redo pass and k_path.
+__global__ void k_check_pair_rcp(const double* in, int n, int huge, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    StageOps a, b;
+    a.rc = in[4 * i];
+    a.st = in[4 * i + 1];
+    b.rc = in[4 * i + 2];
+    b.st = in[4 * i + 3];
+    a.ct = b.ct = 0.0;
+    if (huge) {
+        stage_x<true>(a);
+        stage_x<true>(b);
+    } else {
+        stage_x<false>(a);
+        stage_x<false>(b);
+    }
+    double wa, wb;
+    const bool ok = pair_rcp(a, b, wa, wb);
+    out[5 * i] = -0.5 * (a.st * wa);
+    out[5 * i + 1] = -0.5 * (a.rc * wa);
+    out[5 * i + 2] = -0.5 * (b.st * wb);
+    out[5 * i + 3] = -0.5 * (b.rc * wb);
+    out[5 * i + 4] = ok ? 1.0 : 0.0;
+}
+
 // ---- launch plumbing --------------------------------------------------------------------
 // Launch geometry is cached per device: a process may drive several devices (bhrt_render_frame
 // splits a frame over every visible one) from several host threads. Every cached value is a
@@ -2796,6 +3018,15 @@ extern "C" __attribute__((visibility("default"))) int bhrt_check_seg_len(const d
                                                                          void* stream) {
     if (n <= 0) return 0;
     k_check_seg_len<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_x, n, d_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default"))) int bhrt_check_pair_rcp(const double* d_in, int n,
+                                                                        int huge, double* d_out,
+                                                                        void* stream) {
+    if (n <= 0) return 0;
+    k_check_pair_rcp<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_in, n, huge,
+                                                                                   d_out);
     return (int)hipGetLastError();
 }
 

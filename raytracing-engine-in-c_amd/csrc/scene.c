@@ -189,6 +189,7 @@ int bhrt_fill_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const Accretion
     s->M = bh->mass;
     s->rs = rs;
     s->two_m = 2.0 * bh->mass;
+    s->m_4 = 0.25 * bh->mass; /* exact for every mass of 2^-1020 and above */
     s->rs_x1_5 = rs * 1.5;
     s->rs_x1_05 = rs * 1.05;
     s->rs_x2_5 = rs * 2.5;

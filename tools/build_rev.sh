@@ -5,6 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 REV=$1; NAME=$2; DEFS=${3:-}
 T=$(mktemp -d)
+mkdir -p raytracing-engine-in-c_amd/ab
 git archive "$REV" raytracing-engine-in-c_amd/csrc include | tar -x -C "$T"
 make -s -C "$T/raytracing-engine-in-c_amd/csrc" OUT="$PWD/raytracing-engine-in-c_amd/ab/libbhrt_$NAME.so" DEFS="$DEFS" >/dev/null
 rm -rf "$T"
