@@ -653,6 +653,16 @@ int bhrt_check_seg_len(const double* x, int n, double* out, void* hip_stream);
  * asynchronous on hip_stream. */
 int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hip_stream);
 
+/* Diagnostic: a chained angle shift of the RK4 a = 0 iteration (geodesic.hip shift_chain) on n
+ * cases of a DEVICE array in[4n] = (a, s0, c0, x): sin and cos of x from s0 = sin a, c0 = cos a.
+ * site 0: stage 3 from stage 2's angle (two coefficients, |x - a| <= 1/64); site 1: the advance
+ * of state[1] from stage 4's angle (one coefficient, |x - a| <= 2^-10). d_out[5i..5i+1] = sin x,
+ * cos x of the chained form, d_out[5i+2..5i+3] = those of shift_or_eval on the same operands,
+ * d_out[5i+4] = 1.0 where the short polynomials were kept (0.0: the lane redid the shift with
+ * shift_or_eval, and both pairs are equal bit for bit). Returns 0 or a hipError_t value
+ * (hipErrorInvalidValue for another site); asynchronous on hip_stream. */
+int bhrt_check_shift_chain(const double* in, int n, int site, double* out, void* hip_stream);
+
 /* Copy and optionally reset this thread's statistics (waits for the timed launches, then reads
  * their counters with a synchronous copy on the legacy default stream, i.e. also after the
  * caller's default-stream work). out == NULL with reset != 0 drops the pending launches'

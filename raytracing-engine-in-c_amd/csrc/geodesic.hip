@@ -255,6 +255,54 @@ __device__ __forceinline__ void shift_or_eval(double a, double s0, double c0, do
     }
 }
 
+// shift_or_eval from a NEARER anchor, with shorter polynomials. Two of the RK4
+// a = 0 iteration's six shifts have an angle at hand whose sin and cos are already in registers
+// and that lies a SECOND-order distance from the target, where the iteration's start lies a
+// first-order one (tools/shift_deltas.py; largest |eps| of a 480x270 C2 frame in brackets):
+//   NC = 2  stage 3 from stage 2: theta3 - theta2 = h/2 (k2 - k1)[1]  [0.0086]: two coefficients
+//           each on |eps| <= 1/64, max error 1.2e-18 / 1.7e-21 (tools/shift_poly_fit.py);
+//   NC = 1  the advance of state[1] from stage 4: theta' - theta4      [0.00078]: one coefficient
+//           each on |eps| <= 2^-10, max error 9.8e-19 / 1.3e-22.
+// No lane of camera B's frame, or of frames from inside 15 rs off the polar axis, is beyond
+// either bound, so a wave of mixed rays does not pay for the branch (what a narrower polynomial
+// from the far anchor did: 0.5-0.8% of lanes beyond 1/64). Views down the polar axis, where the
+// |d| <= 10 clamp binds, do have such lanes (0.5-1% beyond 1/64, 0.3-0.5% beyond 2^-10; up to
+// 1.5% beyond 2^-10 from far off-axis cameras); measured on camera A's on-axis frame the short
+// forms still gain 3.7% against 3.8% on camera B (profiles/shiftchain/ab_parent_vs_new.txt).
+// A lane with !(|eps| <= bound) -- NaN included -- redoes the shift with shift_or_eval from the
+// same anchor, whose wide and direct forms treat every operand as before. Per lane, so a ray's
+// rounding never depends on its wave-mates. Returns whether the lane kept the short form.
+// BHRT_SHIFT_CHAIN: 1 both chained sites; 2 the wider alternative of that A/B (the advance alone,
+// two coefficients on 1/64, which no lane of any replayed frame exceeds); 0 every shift from
+// the iteration's start.
+#ifndef BHRT_SHIFT_CHAIN
+#define BHRT_SHIFT_CHAIN 1
+#endif
+template <int NC>
+__device__ __forceinline__ bool shift_chain(double a, double s0, double c0, double x, double& s,
+                                            double& c, Counters* hc) {
+    static_assert(NC == 1 || NC == 2, "one coefficient on 2^-10 or two on 1/64");
+    constexpr double BOUND = NC == 2 ? 0.015625 : 0.0009765625;
+    const double eps = x - a;  // exact when |eps| <= |a| / 2 (Sterbenz), as in shift_or_eval
+    const double z = eps * eps;
+    double sd, cm1;
+    if constexpr (NC == 2) {
+        constexpr double S1 = -0.16666666666059188, S2 = 0.008333261288663034;
+        constexpr double C1 = 0.04166666666580769, C2 = -0.001388879428493602;
+        sd = eps + (z * eps) * fmac_k(z, S2, S1);
+        cm1 = z * __builtin_fma(z, fmac_k(z, C2, C1), -0.5);
+    } else {
+        constexpr double S1 = -0.16666665974827055, C1 = 0.04166666547825309;
+        sd = __builtin_fma(z * eps, S1, eps);
+        cm1 = z * __builtin_fma(z, C1, -0.5);
+    }
+    s = __builtin_fma(c0, sd, __builtin_fma(s0, cm1, s0));
+    c = __builtin_fma(-s0, sd, __builtin_fma(c0, cm1, c0));
+    const bool fast = fabs(eps) <= BOUND;
+    if (__builtin_expect(!fast, 0)) shift_or_eval(a, s0, c0, x, s, c, hc);
+    return fast;
+}
+
 // Trig of theta (= y[1]) for one RK stage: stage 1 takes it from the previous iteration
 // (carried in Ray_), later stages shift it.
 struct Trig1 {
@@ -354,7 +402,8 @@ __device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6],
 #endif
 template <bool SPIN0, bool FAR, bool HUGE>
 __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const Scene& sc,
-                                    bool far_ok, Counters& n, Trig1& tr, bool first) {
+                                    bool far_ok, Counters& n, Trig1& tr, bool first,
+                                    Trig1* keep = nullptr) {
     d[0] = y[3];
     d[1] = y[4];
     d[2] = y[5];
@@ -372,6 +421,8 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
             ct = tr.c;
         } else {
             shift_or_eval(tr.a, tr.s, tr.c, y[1], st, ct, HUGE ? nullptr : &n);
+            // (rk4_step's stage 4: the anchor the advance of state[1] is chained from)
+            if (keep) *keep = Trig1{y[1], st, ct};
         }
         if ((FAR && HUGE) || BHRT_COUNT_STAGES) n.full++;
         // Fast form, straight-line: the same three accelerations with the divisions as one
@@ -500,8 +551,15 @@ __device__ __forceinline__ double rkf45_sum5(double k1, double k3, double k4, do
 // BOTH, and both stages take the literal form with their own reciprocals (accel_fast): a stage
 // never uses a quotient derived from an out-of-range partner. (An Inf, which no sine is, passes
 // the test and turns both members' quotients into NaN, which fail the plain-value test.)
-#ifndef BHRT_PAIR_RCP /* 1: RK4 a = 0 stages 2 and 3 share a reciprocal; 0: each its own */
-#define BHRT_PAIR_RCP 1
+// The same holds one step further (BHRT_PAIR_RCP = 2, the default): x of a stage needs only the
+// position part (components 0, 1) of its state. Stage 2's is y + h/2 y[3..4], known before any
+// acceleration, so x1 and x2 both exist at the top of the iteration; stage 4's is
+// y + h (y[3..4] + h/2 k2[3..4]) -- stage 3's velocities, which need stage 2's accelerations and
+// nothing of stage 3 -- so x3 and x4 both exist once stage 2 is done. Pairs (1,2) and (3,4):
+// two reciprocals per iteration instead of three, no loop-carried register added, and every
+// stage (not two of the four) carries the pair's <= 6 ulp quotient bound.
+#ifndef BHRT_PAIR_RCP /* RK4 a = 0 stages sharing a reciprocal: 2: (1,2) and (3,4); 1: (2,3); 0: none */
+#define BHRT_PAIR_RCP 2
 #endif
 struct StageOps {
     double st, ct, rc, x;  // sin, cos of the stage's theta, its clamped r, x = rc * st (far: 1)
@@ -512,10 +570,14 @@ __device__ __forceinline__ void stage_x(StageOps& o) {  // x and the range test 
     o.x = o.rc * o.st;
     o.ok = (!HUGE ? true : o.rc < 1.0e150) & (fabs(o.st) >= 0.01);
 }
-template <bool FAR, bool HUGE>
+// NC: 0 shifts from tr with shift_or_eval; 1, 2: tr is a chained anchor (shift_chain<NC>)
+template <bool FAR, bool HUGE, int NC = 0>
 __device__ __forceinline__ void stage_ops(double y0, double y1, bool far, const Scene& sc,
                                           Counters& n, const Trig1& tr, StageOps& o) {
-    shift_or_eval(tr.a, tr.s, tr.c, y1, o.st, o.ct, HUGE ? nullptr : &n);
+    if constexpr (NC != 0)
+        shift_chain<NC>(tr.a, tr.s, tr.c, y1, o.st, o.ct, HUGE ? nullptr : &n);
+    else
+        shift_or_eval(tr.a, tr.s, tr.c, y1, o.st, o.ct, HUGE ? nullptr : &n);
     o.rc = max_raw(y0, sc.rs_x1_5);
     stage_x<HUGE>(o);
     if (FAR && far) {
@@ -557,8 +619,73 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
                                          bool far_ok, Counters& n, Trig1& tr,
                                          const double* zs = nullptr) {
     constexpr bool Z = zero_accel<SPIN0, FAR>();
+    // the a = 0 stages' chained anchors (shift_chain): stage 3's theta from stage 2's (CHAIN3),
+    // and t4, stage 4's theta with its sin, cos, handed back in tr for the caller's advance of
+    // state[1] (a stage 2 or 4 on the far-field branch takes no sin, cos: the anchor then
+    // stays tr)
+    constexpr bool CHAIN = SPIN0 && BHRT_SHIFT_CHAIN != 0;
+    constexpr bool CHAIN3 = SPIN0 && BHRT_SHIFT_CHAIN == 1;
     double k[6], acc[6], yt[6];
     const double hh = 0.5 * h;
+    Trig1 t4 = tr;
+    if constexpr (SPIN0 && BHRT_PAIR_RCP == 2) {
+        // stages 1, 2 on one reciprocal and stages 3, 4 on another (pair_rcp). The position
+        // parts formed ahead are the very expressions the stage-state loops would form
+        // (k[0..1] of a stage are its state's [3..4]).
+        const double y20 = y[0] + hh * y[3], y21 = y[1] + hh * y[4];
+        const bool far1 = FAR && far_ok && y[0] > sc.rs_x15;
+        const bool far2 = FAR && far_ok && y20 > sc.rs_x15;
+        StageOps o1, o2, o3, o4;
+        double w1 = 0.0, w2 = 0.0, w3 = 0.0, w4 = 0.0;
+        bool ok = false;
+        Trig1 an = tr;
+        if (!FAR || !(far1 & far2)) {
+            o1.st = tr.s;  // carried from the previous iteration (ray_iterate)
+            o1.ct = tr.c;
+            o1.rc = max_raw(y[0], sc.rs_x1_5);
+            stage_x<HUGE>(o1);
+            if (FAR && far1) {
+                o1.x = 1.0;
+                o1.ok = true;
+            }
+            stage_ops<FAR, HUGE>(y20, y21, far2, sc, n, tr, o2);
+            if (CHAIN3) an = Trig1{y21, o2.st, o2.ct};
+            ok = pair_rcp(o1, o2, w1, w2);
+        }
+        rhs_given<FAR, HUGE>(y, k, sc, far1, n, o1, w1, ok);
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            acc[i] = k[i];
+            yt[i] = i == 0 ? y20 : i == 1 ? y21 : y[i] + hh * k[i];
+        }
+        rhs_given<FAR, HUGE>(yt, k, sc, far2, n, o2, w2, ok);
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            acc[i] = rk4_acc(acc[i], k[i]);
+            yt[i] = y[i] + hh * k[i];
+        }
+        const double y40 = y[0] + h * yt[3], y41 = y[1] + h * yt[4];
+        const bool far3 = FAR && far_ok && yt[0] > sc.rs_x15;
+        const bool far4 = FAR && far_ok && y40 > sc.rs_x15;
+        ok = false;
+        if (!FAR || !(far3 & far4)) {
+            stage_ops<FAR, HUGE, CHAIN3 ? 2 : 0>(yt[0], yt[1], far3, sc, n, an, o3);
+            stage_ops<FAR, HUGE>(y40, y41, far4, sc, n, tr, o4);
+            if (CHAIN) t4 = Trig1{y41, o4.st, o4.ct};
+            ok = pair_rcp(o3, o4, w3, w4);
+        }
+        rhs_given<FAR, HUGE>(yt, k, sc, far3, n, o3, w3, ok);
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            acc[i] = rk4_acc(acc[i], k[i]);
+            yt[i] = i == 0 ? y40 : i == 1 ? y41 : y[i] + h * k[i];
+        }
+        rhs_given<FAR, HUGE>(yt, k, sc, far4, n, o4, w4, ok);
+#pragma unroll
+        for (int i = 0; i < 6; i++) y[i] = __builtin_fma(h6, acc[i] + k[i], y[i]);
+        if (CHAIN) tr = t4;
+        return;
+    }
     rhs<SPIN0, FAR, HUGE>(y, k, sc, far_ok, n, tr, true);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
@@ -576,7 +703,10 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         bool ok = false;
         if (!FAR || !(far2 & far3)) {
             stage_ops<FAR, HUGE>(yt[0], yt[1], far2, sc, n, tr, o2);
-            stage_ops<FAR, HUGE>(y30, y31, far3, sc, n, tr, o3);
+            if constexpr (CHAIN3)
+                stage_ops<FAR, HUGE, 2>(y30, y31, far3, sc, n, Trig1{yt[1], o2.st, o2.ct}, o3);
+            else
+                stage_ops<FAR, HUGE>(y30, y31, far3, sc, n, tr, o3);
             ok = pair_rcp(o2, o3, w2, w3);
         }
         rhs_given<FAR, HUGE>(yt, k, sc, far2, n, o2, w2, ok);
@@ -600,7 +730,9 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         acc[i] = rk4_acc(acc[i], k[i]);
         yt[i] = (Z && i >= 3) ? y[i] : y[i] + h * k[i];
     }
-    rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
+    // (BHRT_PAIR_RCP = 1 or 0 with the chained advance: stage 4 leaves its anchor in t4; with 0
+    // stage 3 keeps its shift from tr)
+    rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false, CHAIN ? &t4 : nullptr);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
         // h * (...) / 6 as (h * RN(1/6)) * (...), h6 = h * RN(1/6) (the caller's): the increment
@@ -610,6 +742,7 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         else if (!(Z && i >= 3))
             y[i] = __builtin_fma(h6, acc[i] + k[i], y[i]);
     }
+    if (CHAIN) tr = t4;
 }
 
 // RKF45's accept test (math_util.c:367-391, 402-434): accept iff
@@ -1250,7 +1383,18 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
         // sin, cos of state[1] feed only the a = 0 accelerations (rhs); the Kerr branch
         // (a != 0, accelerations 0) never reads them, and the compiler keeps a dead
         // loop-carried advance alive otherwise (C5: 45 instructions of the loop)
-        if (SPIN0) trig_advance(tr.a, R.y[1], R.s1, R.c1, hc);
+        if constexpr (SPIN0 && METHOD == INTEGRATOR_RK4 && BHRT_SHIFT_CHAIN) {
+            // from stage 4's theta, sin, cos (rk4_step left them in tr), a second-order distance
+            // away: one coefficient (shift_chain; two with BHRT_SHIFT_CHAIN = 2). The carried
+            // pair now passes through two shifts per iteration, stage 4's and this one
+            // (DESIGN.md §2.3).
+            double s1, c1;
+            shift_chain<BHRT_SHIFT_CHAIN == 1 ? 1 : 2>(tr.a, tr.s, tr.c, R.y[1], s1, c1, hc);
+            R.s1 = s1;
+            R.c1 = c1;
+        } else if (SPIN0) {
+            trig_advance(tr.a, R.y[1], R.s1, R.c1, hc);
+        }
         if constexpr (rotation_trig<METHOD, SPIN0, FAR, HUGE>()) {
             // (the rotation for this step size was formed with it, above)
             const double s0 = R.s2, c0 = R.c2;
@@ -2722,6 +2866,27 @@ __global__ void k_check_pair_rcp(const double* in, int n, int huge, double* out)
     out[5 * i + 4] = ok ? 1.0 : 0.0;
 }
 
+// A chained shift (shift_chain) on given operands: case i is (a, s0, c0, x) = in[4i..4i+3], site 0
+// stage 3 from stage 2's angle (two coefficients, |x - a| <= 1/64), site 1 the advance of
+// state[1] from stage 4's angle (one coefficient, |x - a| <= 2^-10). out[5i..5i+1] = sin, cos of x
+// as the chained form gives them, out[5i+2..5i+3] as shift_or_eval does from the same operands,
+// out[5i+4] = 1 if the lane kept the short polynomials, 0 if it redid the shift. Direct
+// evaluations take the redo pass's form (no counters: the library sincos above 2^20).
+__global__ void k_check_shift_chain(const double* in, int n, int site, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double a = in[4 * i], s0 = in[4 * i + 1], c0 = in[4 * i + 2], x = in[4 * i + 3];
+    double s, c, s_ref, c_ref;
+    const bool fast = site == 0 ? shift_chain<2>(a, s0, c0, x, s, c, nullptr)
+                                : shift_chain<1>(a, s0, c0, x, s, c, nullptr);
+    shift_or_eval(a, s0, c0, x, s_ref, c_ref, nullptr);
+    out[5 * i] = s;
+    out[5 * i + 1] = c;
+    out[5 * i + 2] = s_ref;
+    out[5 * i + 3] = c_ref;
+    out[5 * i + 4] = fast ? 1.0 : 0.0;
+}
+
 // ---- launch plumbing --------------------------------------------------------------------
 // Launch geometry is cached per device: a process may drive several devices (bhrt_render_frame
 // splits a frame over every visible one) from several host threads. Every cached value is a
@@ -3027,6 +3192,15 @@ extern "C" __attribute__((visibility("default"))) int bhrt_check_pair_rcp(const 
     if (n <= 0) return 0;
     k_check_pair_rcp<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_in, n, huge,
                                                                                    d_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default"))) int bhrt_check_shift_chain(
+    const double* d_in, int n, int site, double* d_out, void* stream) {
+    if (n <= 0) return 0;
+    if (site != 0 && site != 1) return (int)hipErrorInvalidValue;
+    k_check_shift_chain<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_in, n, site,
+                                                                                      d_out);
     return (int)hipGetLastError();
 }
 

@@ -1,6 +1,8 @@
 """Minimax-style (weighted least squares on Chebyshev nodes, mpmath) fits of sin(d) and
 cos(d) - 1 on |d| <= D for the short shift polynomials of geodesic.hip (sincos_shift).
-Usage: python tools/shift_poly_fit.py 0.0625  -> coefficients (double) and max abs error."""
+Usage: python tools/shift_poly_fit.py 0.0625  -> coefficients (double) and max abs error, for
+one, two and three coefficients each (shift_or_eval: three on 1/16; shift_chain: two on 1/64
+and one on 2^-10 = 0.0009765625)."""
 import mpmath as mp
 mp.mp.dps = 50
 D = mp.mpf('0.0625')   # fit interval |delta| <= D (slightly above the 0.05 used, margin)
@@ -26,7 +28,7 @@ def fit_cos(n):
     rhs = [(mp.cos(p) - 1 + p**2/2) / p**4 for p in pts]
     w = [p**4 for p in pts]
     return lsq(rows, rhs, w)
-for n in (2, 3):
+for n in (1, 2, 3):
     S = fit_sin(n); C = fit_cos(n)
     Sd = [float(x) for x in S]; Cd = [float(x) for x in C]
     # max abs error with double coefficients (exact arithmetic)
