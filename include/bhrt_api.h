@@ -663,6 +663,16 @@ int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hi
  * (hipErrorInvalidValue for another site); asynchronous on hip_stream. */
 int bhrt_check_shift_chain(const double* in, int n, int site, double* out, void* hip_stream);
 
+/* Diagnostic: a guard of the trace loop that is decided from the high words of its f64 operands
+ * (geodesic.hip BHRT_GUARD_WORDS), beside the exact test it filters for, on n cases of DEVICE
+ * arrays. kind 0 (the one guard built): the plain-value test of a stage's three accelerations,
+ * a[3n] (b is not read and may be NULL). d_out[2i] = 1 where the high-word filter keeps the case
+ * on the straight-line path, d_out[2i+1] = 1 where the exact test (every |a| <= 10) passes; the
+ * first implies the second. Returns 0 or a hipError_t value (hipErrorInvalidValue for another
+ * kind); asynchronous on hip_stream. */
+int bhrt_check_guard_words(const double* a, const double* b, int n, int kind, int* out,
+                           void* hip_stream);
+
 /* Copy and optionally reset this thread's statistics (waits for the timed launches, then reads
  * their counters with a synchronous copy on the legacy default stream, i.e. also after the
  * caller's default-stream work). out == NULL with reset != 0 drops the pending launches'

@@ -112,6 +112,8 @@ _PROTOS = {
     "bhrt_trace_paths": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                    _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                    C.c_int, C.c_int, _P(abi.Paths), _P(abi.FrameSoA)]),
+    "bhrt_check_guard_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
     "bhrt_shard_rows": (C.c_int, [C.c_int, _P(abi.Rows)]),
     "bhrt_get_stats": (C.c_int, [_P(abi.Stats), C.c_int]),
     "bhrt_device_count": (C.c_int, []),
@@ -437,6 +439,12 @@ def set_claim_order(d_order_ptr, n):
     thread's next device camera frames of n rays; None / 0 = the default order. Raises if the
     array is not a permutation of [0, n)."""
     _check(load().bhrt_set_claim_order(d_order_ptr, int(n)), "bhrt_set_claim_order")
+
+
+def check_guard_words(a_ptr, b_ptr, n, kind, out_ptr, stream):
+    """bhrt_check_guard_words on device pointers: out[2i] = the high-word filter's answer,
+    out[2i+1] = the exact test's (int32). Returns the call's status (0, or a hipError_t value)."""
+    return load().bhrt_check_guard_words(a_ptr, b_ptr, int(n), int(kind), out_ptr, stream)
 
 
 def shard_rows(height, rows):

@@ -114,6 +114,38 @@ __device__ __forceinline__ double max_abs_raw(double a, double b) {
     return r;
 }
 
+// Guards decided from the HIGH WORDS of their f64 operands. A double's high 32
+// bits hold its sign, exponent and top 20 mantissa bits, so an integer operation on high words
+// can FILTER for a straight-line path: it may send a lane that belongs on the fast path to the
+// rare block -- which first makes the exact f64 test and sends such a lane back -- and never lets
+// a lane that fails the exact test through. The results are then the exact test's, bit for bit.
+// Only forms that SAVE INSTRUCTIONS are built: a 32-bit compare of one high word issues no
+// faster than the f64 compare it would replace (4 cycles either way beside an f64 stream, at 1
+// and at 4 waves per SIMD: tools/probe/cmp_probe.hip, profiles/guardwords/cmp_probe.txt).
+// BHRT_GUARD_WORDS = 1: the filter in the RK4 stage pairs (rhs_given: C2 +1.3%, C1 +1.9% same-box);
+// 2: in the single-stage form (rhs) too, which RKF45 runs -- C3 -3.6% same-box, its kernel gains
+// scratch (profiles/guardwords/ab_parent_vs_new.txt), so that is not the default; 0: every
+// guard is the exact f64 test alone, the kernels of the commit before.
+#ifndef BHRT_GUARD_WORDS
+#define BHRT_GUARD_WORDS 1
+#endif
+// the high word of x: a sub-register read, no instruction
+__device__ __forceinline__ unsigned hiword(double x) {
+    return (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 32);
+}
+// Filter for "a, b and c are all plain values of magnitude <= 10" (accel_fast): bit 30 of a
+// high word -- the top bit of the 11-bit exponent field -- is set exactly when the double is
+// NaN, +-Inf or at least 2 in magnitude (biased exponent >= 1024), so it is clear in the OR of
+// the three exactly when all three are finite and below 2. Read as a float the OR has bit 30
+// clear exactly when its magnitude is below 2.0f (biased exponent < 128; a NaN pattern fails the
+// ordered compare as it must): one v_or3_b32 and one v_cmp_lt_f32 with the |.| modifier, where
+// the exact test is three v_cmp_le_f64 and two s_and_b64. true implies the exact test passes; a
+// lane with some |value| in [2, 10] gets false and is sent back by the exact test.
+__device__ __forceinline__ bool all_below_2(double a, double b, double c) {
+    const unsigned w = hiword(a) | hiword(b) | hiword(c);
+    return __builtin_fabsf(__builtin_bit_cast(float, w)) < 2.0f;
+}
+
 // sin and cos of one argument, for the trace loop. OCML's sincos
 // spends ~78 VALU per call on a range reduction valid to 2^30+; every argument here (the
 // radius read as an angle by ray_derivatives, theta, phi) stays far below 2^20, where a
@@ -364,7 +396,7 @@ __device__ __forceinline__ void repair_clamp(double (&d)[6]) {
 // where it is tested, rc < 1e150, of this stage and of the one it shares the reciprocal with.
 // A lane that fails it, or whose result is not a plain |d| <= 10 value, recomputes the stage in
 // the literal form (its own reciprocals) before the repair and clamps.
-template <bool HUGE>
+template <bool HUGE, bool WORDS = BHRT_GUARD_WORDS != 0>
 __device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6], const Scene& sc,
                                            double st, double ct, double rc, double w2, bool ok) {
     // The factor -2 of d4 and d5 rides on the reciprocal (w2 = -2 / (r sin theta), rcp_nr_m2):
@@ -379,6 +411,12 @@ __device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6],
     const double p2 = y[3] * yr2;
     d[4] = __builtin_fma(p2, y[4], u * (ct * y[5]));
     d[5] = y[5] * __builtin_fma(y[4], ct * ys2, p2);
+    // WORDS: the straight-line path's guard is the high-word filter (all_below_2: 2 VALU for the
+    // exact test's 3, and two scalar ANDs less); a lane it holds back -- some |d| in [2, 10], or
+    // truly out of range -- takes the exact test first, in the rare block, so the lanes that go
+    // on to the literal form are exactly the exact test's
+    if constexpr (WORDS)
+        if (__builtin_expect((int)ok & (int)all_below_2(d[3], d[4], d[5]), 1)) return;
     const int plain = (int)ok & (int)(fabs(d[3]) <= 10.0) & (int)(fabs(d[4]) <= 10.0) &
                       (int)(fabs(d[5]) <= 10.0);
     if (__builtin_expect(plain, 1)) return;
@@ -442,7 +480,7 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
         // derivative is the clamped |d3| <= 10 (or 0), so |state[0]| <= 0.1 * 20 * steps^2;
         // k_path (a caller-given t) and the HUGE redo keep it
         const bool ok = (!HUGE ? true : rc < 1.0e150) & (fabs(st) >= 0.01);
-        accel_fast<HUGE>(y, d, sc, st, ct, rc, rcp_nr_m2(rc * st), ok);
+        accel_fast<HUGE, BHRT_GUARD_WORDS == 2>(y, d, sc, st, ct, rc, rcp_nr_m2(rc * st), ok);
         return;
     }
     // :131-138
@@ -2887,6 +2925,18 @@ __global__ void k_check_shift_chain(const double* in, int n, int site, double* o
     out[5 * i + 4] = fast ? 1.0 : 0.0;
 }
 
+// A high-word guard (BHRT_GUARD_WORDS) beside the exact test it filters for, on given operands.
+// kind 0, the one guard built: accel_fast's plain-value test of a stage's three accelerations
+// a[3i..3i+2] (b is not read). out[2i] = the filter's answer (all_below_2), out[2i+1] = the exact
+// test's (every |a| <= 10, NaN failing).
+__global__ void k_check_guard_words(const double* a, const double* /*b*/, int n, int* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double d3 = a[3 * i], d4 = a[3 * i + 1], d5 = a[3 * i + 2];
+    out[2 * i] = all_below_2(d3, d4, d5);
+    out[2 * i + 1] = (int)(fabs(d3) <= 10.0) & (int)(fabs(d4) <= 10.0) & (int)(fabs(d5) <= 10.0);
+}
+
 // ---- launch plumbing --------------------------------------------------------------------
 // Launch geometry is cached per device: a process may drive several devices (bhrt_render_frame
 // splits a frame over every visible one) from several host threads. Every cached value is a
@@ -3200,6 +3250,15 @@ extern "C" __attribute__((visibility("default"))) int bhrt_check_shift_chain(
     if (n <= 0) return 0;
     if (site != 0 && site != 1) return (int)hipErrorInvalidValue;
     k_check_shift_chain<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_in, n, site,
+                                                                                      d_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default"))) int bhrt_check_guard_words(
+    const double* d_a, const double* d_b, int n, int kind, int* d_out, void* stream) {
+    if (n <= 0) return 0;
+    if (kind != 0) return (int)hipErrorInvalidValue;
+    k_check_guard_words<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(d_a, d_b, n,
                                                                                       d_out);
     return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
 """Render one frame with the library in BHRT_LIB and save it (npz), or compare two saves:
-  BHRT_LIB=... python tools/diff_libs.py save C1 out.npz
+  BHRT_LIB=... python tools/diff_libs.py save C1 out.npz [camera, default B]
   python tools/diff_libs.py cmp a.npz b.npz
 Used to see how far an arithmetic variant moves the outputs (classes, steps, floats)."""
 import os
@@ -15,7 +15,7 @@ if sys.argv[1] == "save":
     c = configs.CONFIGS[sys.argv[2]]
     bh, dk, cfg = c.scene()
     W, H = c.frame(1).width, c.frame(1).height  # (C5: the whole 7680x4320 image)
-    f = lib.render_frame(bh, dk, cfg, configs.camera("B"), W, H, c.method, c.flags)
+    f = lib.render_frame(bh, dk, cfg, configs.camera(sys.argv[4] if len(sys.argv) > 4 else "B"), W, H, c.method, c.flags)
     np.savez(sys.argv[3], **f)
 else:
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])

@@ -19,6 +19,11 @@ fast path with probability 1 - (1 - p)^64, p the lane fraction beyond T. Where t
 1e-4 (marked "ok") a narrower polynomial on T costs no wave its branch; where it is not, measure
 (profiles/shiftchain/ab_parent_vs_new.txt: the views down the polar axis).
 
+The replay also counts what the high-word filter of the plain-value test (all_below_2,
+BHRT_GUARD_WORDS) holds back: lane-stages whose raw accelerations hold a |d| >= 2 or a non-finite
+value -- they take the exact |d| <= 10 test in the rare block -- and, of those, the ones the exact
+test fails too (the literal form, as before), with the same tile and mixed-wave figures.
+
   python tools/shift_deltas.py [W H] [--cam B | --cam x,y,z,fov]   (default 480x270, B; CPU only)
 """
 import os
@@ -83,8 +88,15 @@ def replay(cam, W, H, oracle=None):
             out[3] = -M / (r * r * f) * f + r * v_th * v_th + r * sn * sn * v_ph * v_ph
             out[4] = -2.0 * v_r * v_th / r + sn * np.cos(th) * v_ph * v_ph
             out[5] = -2.0 * v_r * v_ph / r - 2.0 * v_th * v_ph * np.cos(th) / sn
+        with np.errstate(invalid="ignore"):
+            mag = np.abs(out[3:])
+            flags.append((~(mag < 2.0).all(axis=0), ~(mag <= 10.0).all(axis=0)))
         out[3:] = np.clip(np.nan_to_num(out[3:], nan=0.0, posinf=0.0, neginf=0.0), -10, 10)
         return out
+
+    flags = []  # per stage of the current iteration: (some |d| >= 2 or non-finite, exact test fails)
+    accel = dict(stage_evals=0, wave_stage_evals=0, lane_over2=0, wave_over2=0, lane_over10=0,
+                 wave_over10=0)
 
     out = {s: dict(lane_over=np.zeros(len(TS)), wave_over=np.zeros(len(TS)), max=0.0)
            for s in SITES}
@@ -101,6 +113,7 @@ def replay(cam, W, H, oracle=None):
         h = np.where(r < rs * 2.5, min(dt * 0.001, 0.1),
                      np.where(r < rs * 5, min(dt * 0.01, 0.1),
                               np.where(r < rs * 15, min(dt * 0.1, 0.1), min(dt, 0.1))))
+        flags.clear()
         k1 = derivs(y)
         k2 = derivs(y + 0.5 * h * k1)
         k3 = derivs(y + 0.5 * h * k2)
@@ -120,8 +133,15 @@ def replay(cam, W, H, oracle=None):
                 over = alive & (a > T)
                 out[s]["lane_over"][j] += over.sum()
                 out[s]["wave_over"][j] += (np.bincount(tile[over], minlength=ntile) > 0).sum()
+        for over2, over10 in flags:
+            accel["stage_evals"] += int(alive.sum())
+            accel["wave_stage_evals"] += int(tiles_alive.sum())
+            for name, f in (("over2", over2), ("over10", over10)):
+                accel["lane_" + name] += int((alive & f).sum())
+                accel["wave_" + name] += int((np.bincount(tile[alive & f], minlength=ntile) > 0).sum())
         y = np.where(alive, ynew, y)
     out["lane_evals"], out["wave_evals"] = lane_evals, wave_evals
+    out["accel"] = accel
     return out
 
 
@@ -152,6 +172,14 @@ def main(argv):
             cells.append(f"{p:9.2e} {res[s]['wave_over'][j] / we:9.2e} {m:9.2e}"
                          f"{' ok' if m <= MODEL_MAX else '   '}")
         print(f"{s:13s} {res[s]['max']:10.3e}  " + "  ".join(cells))
+    a = res["accel"]
+    print(f"plain-value test, {a['stage_evals']} lane-stages, {a['wave_stage_evals']} tile-stages: "
+          "lane fraction, 8x8-tile fraction, mixed-wave model")
+    for name, what in (("over2", "held back by the high-word filter (some |d| >= 2 or non-finite)"),
+                       ("over10", "failing the exact test too (literal form)")):
+        p = a["lane_" + name] / a["stage_evals"]
+        print(f"  {what:66s} {p:9.2e} {a['wave_' + name] / a['wave_stage_evals']:9.2e} "
+              f"{mixed_wave(p):9.2e}")
 
 
 if __name__ == "__main__":
