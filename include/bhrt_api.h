@@ -708,6 +708,87 @@ int bhrt_set_claim_order(const int* d_order, int n);
 int bhrt_update_particles_steps(ParticleSystem* system, const BlackHoleParams* blackhole,
                                 const SimulationConfig* config, int steps, double* kernel_ms);
 
+/* ---- device-resident particle systems: update and extract on the GPU ---- */
+
+/* The visualizer's physics tick (bh_update_particles, then bh_get_particle_data into vertex
+ * arrays, renderer.cpp:926-951, :1153-1219) on an object that keeps the Particle array on the
+ * device: a tick is the update kernel and a few bytes per ACTIVE particle, no copy of the array.
+ * update_particles, bhrt_update_particles_steps and the bh_* particle functions are unchanged.
+ * THE RULE:
+ *  State.    The object holds system->particles[0 .. count) on the device that was current at
+ *            creation. create and upload copy the array in and WAIT for the copy. upload is for
+ *            use after the caller changed the host system (add_particle, remove_particle); it may
+ *            change count.
+ *  Update.   bhrt_particles_update_device(ps, bh, cfg, s, stream) leaves the resident array in
+ *            exactly the state bhrt_update_particles_steps(host_system, bh, cfg, s, NULL) leaves
+ *            the host array in: every field of every particle bit for bit, the Inf/NaN of diverged
+ *            test particles and the active flags of captured particles included; steps == 0 is a
+ *            no-op. Asynchronous with NO host wait; `updates` advances AT THE CALL.
+ *  Extract.  bh_get_particle_data on the resident array with *count = max_count: the first
+ *            min(A, max_count) ACTIVE particles in array order, A the number of active particles.
+ *            positions, velocities and types are copied, ids holds Particle.id, xyz32 and vel32 are
+ *            (float) of the same doubles, count[0] is the number written. Elements at or beyond
+ *            count[0] are NOT WRITTEN. The order is deterministic -- no atomic decides where a
+ *            particle lands -- and the result is the same bits run to run and on any stream.
+ *            bhrt_particles_extract does the same into HOST arrays and returns when they are
+ *            complete; host elements beyond the count keep what they held.
+ *  Download. Writes the resident particles into system->particles; refuses unless system->count
+ *            equals the resident count; the system's other members are untouched. Waits for the
+ *            copy.
+ *  Streams.  hip_stream as for bhrt_render_frame_device: a stream is used as given, NULL is
+ *            ordered like the legacy default stream. The calls of one object share its arrays, so
+ *            THE CALLER ORDERS THEM, as for an accumulator: the same stream for every call on an
+ *            object, or the caller's own events between the streams it uses. Objects are
+ *            independent of each other. The calls that wait (upload, the host extract, download,
+ *            destroy) first wait for the stream of the object's last update or device extract.
+ *  Refusals. -1 with bhrt_last_error set, nothing written and no state changed, each decided
+ *            BEFORE ANY HIP CALL: a NULL object, system, blackhole or config; system->count < 1 or
+ *            NULL system->particles; steps < 0; max_count < 1; an output struct that is NULL or
+ *            has all seven pointers NULL; a download count mismatch; a current device other than
+ *            the object's. HIP failures also return -1. */
+typedef struct bhrt_particles bhrt_particles;   /* opaque; owned by the thread and device that made it */
+
+typedef struct {          /* DEVICE arrays (HOST for bhrt_particles_extract); any may be NULL      */
+    double*  positions;   /* [max_count][3]  bh_get_particle_data's positions                      */
+    double*  velocities;  /* [max_count][3]                                                        */
+    int32_t* types;       /* [max_count]                                                           */
+    int32_t* ids;         /* [max_count]     Particle.id                                           */
+    float*   xyz32;       /* [max_count][3]  (float) of positions: a GL vertex buffer              */
+    float*   vel32;       /* [max_count][3]  (float) of velocities                                 */
+    int32_t* count;       /* [1]             particles written = min(active, max_count)            */
+} bhrt_particle_data;
+
+typedef struct { int32_t count, device; int64_t updates; } bhrt_particles_state;
+
+/* A resident copy of system->particles[0 .. count) on the CURRENT device: 152 B per particle and
+ * 8 B per 256 particles. Returns 0 and the handle in *ps, or -1 with *ps untouched. */
+int  bhrt_particles_create(const ParticleSystem* system, bhrt_particles** ps);
+/* The host system's array again (any count >= 1; the device buffer grows with slack). */
+int  bhrt_particles_upload(bhrt_particles* ps, const ParticleSystem* system);
+int  bhrt_particles_update_device(bhrt_particles* ps, const BlackHoleParams* blackhole,
+                                  const SimulationConfig* config, int steps, void* hip_stream);
+int  bhrt_particles_extract_device(bhrt_particles* ps, int max_count,
+                                   const bhrt_particle_data* device_out, void* hip_stream);
+int  bhrt_particles_extract(bhrt_particles* ps, int max_count, const bhrt_particle_data* host_out);
+int  bhrt_particles_download(bhrt_particles* ps, ParticleSystem* system);
+/* The resident array itself, for zero-copy reading in stream order (either pointer may be NULL). */
+int  bhrt_particles_device_buffer(const bhrt_particles* ps, const Particle** device_particles,
+                                  int* count);
+/* The host-side state. No HIP call. */
+int  bhrt_particles_info(const bhrt_particles* ps, bhrt_particles_state* state);
+/* Frees the object once the device has finished with it (waits for the device). NULL: no-op. */
+void bhrt_particles_destroy(bhrt_particles* ps);
+
+/* A measurement aid (tools/bench_particles_resident.py): two update steps with the plain
+ * kernel, two with the counting kernel (the second of each timed: both then follow an update pass
+ * over the array), then the scan and the scatter of an extract into device_out, then the count pass
+ * of create and upload, each between HIP events on libbhrt's own stream; waits, and returns the
+ * five kernel times in ms[0..4]. The resident array advances by four steps (`updates` by 4).
+ * Refusals as for the calls it makes. */
+int  bhrt_particles_kernel_ms(bhrt_particles* ps, const BlackHoleParams* blackhole,
+                              const SimulationConfig* config, int max_count,
+                              const bhrt_particle_data* device_out, double ms[5]);
+
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);
 

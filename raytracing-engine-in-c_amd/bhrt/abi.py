@@ -213,6 +213,23 @@ def particles_view(ps):
     return np.frombuffer(buf, dtype=PARTICLE_DTYPE)
 
 
+PARTICLE_DATA_FIELDS = ("positions", "velocities", "types", "ids", "xyz32", "vel32", "count")
+# per element of bhrt_particle_data: (trailing shape, dtype)
+PARTICLE_DATA_SHAPES = {"positions": ((3,), np.float64), "velocities": ((3,), np.float64),
+                        "types": ((), np.int32), "ids": ((), np.int32),
+                        "xyz32": ((3,), np.float32), "vel32": ((3,), np.float32)}
+
+
+class ParticleData(C.Structure):
+    """bhrt_particle_data: device (or host) arrays of max_count elements, count [1]; any None."""
+    _fields_ = [(f, C.c_void_p) for f in PARTICLE_DATA_FIELDS]
+
+
+class ParticlesState(C.Structure):
+    """bhrt_particles_state: the host-side state of a device-resident particle system."""
+    _fields_ = [("count", C.c_int32), ("device", C.c_int32), ("updates", C.c_int64)]
+
+
 assert C.sizeof(Particle) == 152 and C.sizeof(ParticleSystem) == 32
 assert C.sizeof(RayTraceHit) == 160 and C.sizeof(SimulationConfig) == 72
 assert C.sizeof(BlackHoleParams) == 64 and C.sizeof(AccretionDiskParams) == 48

@@ -99,6 +99,20 @@ _PROTOS = {
                                    _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
                                    _P(abi.Camera), C.c_int, C.c_int, _P(abi.SupersamplingParams),
                                    _P(abi.AccumOut)]),
+    "bhrt_particles_create": (C.c_int, [_P(abi.ParticleSystem), _P(C.c_void_p)]),
+    "bhrt_particles_upload": (C.c_int, [C.c_void_p, _P(abi.ParticleSystem)]),
+    "bhrt_particles_update_device": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
+                                               _P(abi.SimulationConfig), C.c_int, C.c_void_p]),
+    "bhrt_particles_extract_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.ParticleData),
+                                                C.c_void_p]),
+    "bhrt_particles_extract": (C.c_int, [C.c_void_p, C.c_int, _P(abi.ParticleData)]),
+    "bhrt_particles_download": (C.c_int, [C.c_void_p, _P(abi.ParticleSystem)]),
+    "bhrt_particles_device_buffer": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int)]),
+    "bhrt_particles_info": (C.c_int, [C.c_void_p, _P(abi.ParticlesState)]),
+    "bhrt_particles_destroy": (None, [C.c_void_p]),
+    "bhrt_particles_kernel_ms": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
+                                           _P(abi.SimulationConfig), C.c_int,
+                                           _P(abi.ParticleData), _P(C.c_double * 5)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -401,6 +415,90 @@ def accum_frame(acc, bh, dk, cfg, cam, method=abi.INTEGRATOR_RK4, flags=0, ss=No
     _check(load().bhrt_accum_frame(acc, _ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), method, flags,
                                    _ptr(ss), C.byref(out)), "bhrt_accum_frame")
     return arrays
+
+
+def particles_create(system):
+    """bhrt_particles_create on the current device: a resident copy of the abi.ParticleSystem's
+    particles; the handle (an int) for the particles_* calls, freed with particles_destroy."""
+    h = C.c_void_p()
+    _check(load().bhrt_particles_create(_ptr(system), C.byref(h)), "bhrt_particles_create")
+    return h.value
+
+
+def particles_destroy(ps):
+    load().bhrt_particles_destroy(ps)
+
+
+def particles_upload(ps, system):
+    """bhrt_particles_upload: the host system's array again (its count may have changed)."""
+    _check(load().bhrt_particles_upload(ps, _ptr(system)), "bhrt_particles_upload")
+
+
+def particles_update_device(ps, bh, cfg, steps=1, stream=None):
+    """bhrt_particles_update_device: `steps` update_particles steps of the resident array,
+    asynchronous on a hipStream_t (int handle or None)."""
+    _check(load().bhrt_particles_update_device(ps, _ptr(bh), _ptr(cfg), int(steps),
+                                               C.c_void_p(stream) if stream else None),
+           "bhrt_particles_update_device")
+
+
+def particle_data(tensors):
+    """abi.ParticleData pointing at device tensors (torch) keyed by abi.PARTICLE_DATA_FIELDS."""
+    return abi.ParticleData(**{f: t.data_ptr() for f, t in tensors.items()})
+
+
+def particles_extract_device(ps, max_count, out, stream=None):
+    """bhrt_particles_extract_device: bh_get_particle_data of the resident array into the device
+    arrays of `out` (abi.ParticleData), asynchronous on a hipStream_t (int handle or None)."""
+    _check(load().bhrt_particles_extract_device(ps, int(max_count), _ptr(out),
+                                                C.c_void_p(stream) if stream else None),
+           "bhrt_particles_extract_device")
+
+
+def particles_extract(ps, max_count, fields=abi.PARTICLE_DATA_FIELDS, fill=0):
+    """bhrt_particles_extract into host numpy arrays of max_count elements (a dict of `fields`;
+    elements at and beyond count[0] keep `fill`)."""
+    arrays = {}
+    for f in fields:
+        if f == "count":
+            arrays[f] = np.full(1, fill, dtype=np.int32)
+        else:
+            tail, dtype = abi.PARTICLE_DATA_SHAPES[f]
+            arrays[f] = np.full((int(max_count),) + tail, fill, dtype=dtype)
+    out = abi.ParticleData(**{f: a.ctypes.data for f, a in arrays.items()})
+    _check(load().bhrt_particles_extract(ps, int(max_count), C.byref(out)),
+           "bhrt_particles_extract")
+    return arrays
+
+
+def particles_download(ps, system):
+    """bhrt_particles_download: the resident particles into system.particles (equal counts)."""
+    _check(load().bhrt_particles_download(ps, _ptr(system)), "bhrt_particles_download")
+
+
+def particles_device_buffer(ps):
+    """bhrt_particles_device_buffer: (device address of the Particle array, count)."""
+    p, n = C.c_void_p(), C.c_int()
+    _check(load().bhrt_particles_device_buffer(ps, C.byref(p), C.byref(n)),
+           "bhrt_particles_device_buffer")
+    return p.value, n.value
+
+
+def particles_state(ps):
+    """bhrt_particles_info: the host-side state as a dict (count, device, updates)."""
+    s = abi.ParticlesState()
+    _check(load().bhrt_particles_info(ps, C.byref(s)), "bhrt_particles_info")
+    return {f: getattr(s, f) for f, _ in abi.ParticlesState._fields_}
+
+
+def particles_kernel_ms(ps, bh, cfg, max_count, out):
+    """bhrt_particles_kernel_ms: HIP-event times (ms) of a plain update, a counting update (each
+    the second of two), the scan, the scatter into the device arrays of `out` and the count pass;
+    the resident array advances four steps."""
+    ms = (C.c_double * 5)()
+    _check(load().bhrt_particles_kernel_ms(ps, _ptr(bh), _ptr(cfg), int(max_count), _ptr(out),
+                                           C.byref(ms)), "bhrt_particles_kernel_ms")
+    return dict(zip(("update_plain", "update_counted", "scan", "scatter", "count_pass"), ms))
 
 
 def trace_paths_device(rays_ptr, n, bh, dk, cfg, method, max_positions, every, paths, hits,

@@ -282,6 +282,26 @@ typedef struct {
 int bhrt_launch_particles(Particle* d_particles, int count, const bhrt_particle_k* k, int steps,
                           void* stream, void* ev0, void* ev1);
 
+/* Device-resident particle systems (particles_resident.c; the rule: include/bhrt_api.h). All
+ * asynchronous on `stream`, ev0/ev1 as above, 0 or a hipError_t value. With nblocks =
+ * (count + 255) / 256, the 256-lane workgroups of the update:
+ *   _counted  bhrt_launch_particles' update, and d_block_active[b] = workgroup b's particles active
+ *             after it (d_block_active [nblocks]);
+ *   _count    d_block_active of the array as it stands, no update;
+ *   _scan     d_offsets [nblocks + 1] = the exclusive scan of d_block_active, the total last; one
+ *             workgroup, no workgroup waits for another;
+ *   _scatter  bh_get_particle_data into the DEVICE arrays of `out` by those offsets. */
+int bhrt_launch_particles_counted(Particle* d_particles, int count, const bhrt_particle_k* k,
+                                  int steps, int* d_block_active, void* stream, void* ev0,
+                                  void* ev1);
+int bhrt_launch_particles_count(const Particle* d_particles, int count, int* d_block_active,
+                                void* stream);
+int bhrt_launch_particles_scan(const int* d_block_active, int nblocks, int* d_offsets, void* stream,
+                               void* ev0, void* ev1);
+int bhrt_launch_particles_scatter(const Particle* d_particles, int count, const int* d_offsets,
+                                  int max_count, const bhrt_particle_data* out, void* stream,
+                                  void* ev0, void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */

@@ -113,13 +113,11 @@ __device__ __forceinline__ void step_newtonian(Particle& p, const bhrt_particle_
     p.position.z = p.position.z + p.velocity.z * k.dt;
 }
 
-__global__ __launch_bounds__(256) void k_update_particles(Particle* ps, int count,
-                                                          const bhrt_particle_k k, int steps) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+// update_particles body (:519-562) for particle i: `steps` updates in registers; the active flag after
+__device__ __forceinline__ int update_one(Particle* ps, int i, const bhrt_particle_k& k, int steps) {
     Particle p = ps[i];
     const double rs20 = 20.0 * k.rs;
-    for (int s = 0; s < steps && p.active; s++) {  // update_particles body (:519-562)
+    for (int s = 0; s < steps && p.active; s++) {
         p.age += k.dt;
         const double r = length3(p.position);
         if (p.type == PARTICLE_TEST && r < rs20)
@@ -129,6 +127,139 @@ __global__ __launch_bounds__(256) void k_update_particles(Particle* ps, int coun
         if (length3(p.position) <= k.rs) p.active = 0;
     }
     ps[i] = p;
+    return p.active;
+}
+
+// the workgroup's count of set flags into block_active[blockIdx.x]: a ballot per wave, the four
+// waves' counts summed through LDS. Every lane of the workgroup calls it (a barrier inside). In
+// the update kernel it costs nothing that HIP events can see (profiles/particles_resident).
+__device__ __forceinline__ void block_count(bool active, int* block_active) {
+    __shared__ int wave_count[4];
+    const unsigned long long m = __ballot(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        block_active[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+}
+
+// COUNT = false: the kernel of update_particles and bhrt_update_particles_steps. COUNT = true
+// (device-resident systems, particles_resident.c): the same arithmetic, and the workgroup's number
+// of particles active AFTER the update into block_active[blockIdx.x]; lanes past count add 0 and
+// stay for the barrier.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_update_particles(Particle* ps, int count,
+                                                          const bhrt_particle_k k, int steps,
+                                                          int* block_active) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (!COUNT) {
+        if (i >= count) return;
+        (void)update_one(ps, i, k, steps);
+    } else {
+        int active = 0;
+        if (i < count) active = update_one(ps, i, k, steps);
+        block_count(active != 0, block_active);
+    }
+}
+
+// block_active[] of an array as it stands (after an upload): the flags alone are read
+__global__ __launch_bounds__(256) void k_particles_count(const Particle* ps, int count,
+                                                         int* block_active) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    block_count(i < count && ps[i].active != 0, block_active);
+}
+
+// Exclusive scan of block_active[0, nblocks) into offsets[0, nblocks], offsets[nblocks] = the
+// total. ONE workgroup walks the array in chunks of 256 x kScanItems with a running carry: no
+// workgroup waits for another, whatever the size.
+constexpr int kScanItems = 16;
+__global__ __launch_bounds__(256) void k_particles_scan(const int* block_active, int nblocks,
+                                                        int* offsets) {
+    __shared__ int wave_sum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < nblocks; base += 256 * kScanItems) {
+        const int first = base + (int)threadIdx.x * kScanItems;
+        int v[kScanItems];
+        int mine = 0;
+#pragma unroll
+        for (int j = 0; j < kScanItems; j++) {
+            v[j] = first + j < nblocks ? block_active[first + j] : 0;
+            mine += v[j];
+        }
+        int incl = mine;  // inclusive scan of the lanes' sums within the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < wave; w++) before += wave_sum[w];
+        const int chunk = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+        __syncthreads();  // wave_sum is rewritten by the next chunk
+        int run = before + (incl - mine);
+#pragma unroll
+        for (int j = 0; j < kScanItems; j++) {
+            if (first + j < nblocks) offsets[first + j] = run;
+            run += v[j];
+        }
+        carry += chunk;
+    }
+    if (threadIdx.x == 0) offsets[nblocks] = carry;
+}
+
+// bh_get_particle_data on the device: the active particle of rank r < max_count (its number among
+// the active ones in array order) writes element r of every output. The rank is the workgroup's
+// scanned offset + the set flags of the lower waves (LDS) + those of the lower lanes (ballot), so
+// no atomic decides a place and a wave's stores are contiguous runs. Elements at or beyond the
+// count are not written.
+__global__ __launch_bounds__(256) void k_particles_scatter(const Particle* ps, int count,
+                                                           const int* offsets, int nblocks,
+                                                           int max_count,
+                                                           const bhrt_particle_data out) {
+    __shared__ int wave_count[4];
+    const int base = offsets[blockIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x == 0 && out.count) {
+        const int total = offsets[nblocks];
+        out.count[0] = total < max_count ? total : max_count;
+    }
+    // uniform per workgroup, before the barrier: nothing of this workgroup lands
+    if (base >= max_count || offsets[blockIdx.x + 1] == base) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool active = i < count && ps[i].active != 0;
+    const unsigned long long m = __ballot(active);
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    int rank = base + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) rank += wave_count[w];
+    if (!active || rank >= max_count) return;
+    const Particle* p = ps + i;
+    const size_t r = (size_t)rank, r3 = 3 * (size_t)rank;
+    const Vector3D x = p->position, v = p->velocity;
+    if (out.positions) {
+        out.positions[r3 + 0] = x.x;
+        out.positions[r3 + 1] = x.y;
+        out.positions[r3 + 2] = x.z;
+    }
+    if (out.velocities) {
+        out.velocities[r3 + 0] = v.x;
+        out.velocities[r3 + 1] = v.y;
+        out.velocities[r3 + 2] = v.z;
+    }
+    if (out.types) out.types[r] = (int32_t)p->type;
+    if (out.ids) out.ids[r] = (int32_t)p->id;
+    if (out.xyz32) {
+        out.xyz32[r3 + 0] = (float)x.x;
+        out.xyz32[r3 + 1] = (float)x.y;
+        out.xyz32[r3 + 2] = (float)x.z;
+    }
+    if (out.vel32) {
+        out.vel32[r3 + 0] = (float)v.x;
+        out.vel32[r3 + 1] = (float)v.y;
+        out.vel32[r3 + 2] = (float)v.z;
+    }
 }
 
 }  // namespace
@@ -138,7 +269,48 @@ extern "C" int bhrt_launch_particles(Particle* d, int count, const bhrt_particle
     hipStream_t st = (hipStream_t)stream;
     if (ev0) (void)hipEventRecord((hipEvent_t)ev0, st);
     if (count > 0 && steps > 0)
-        k_update_particles<<<(count + 255) / 256, 256, 0, st>>>(d, count, *k, steps);
+        k_update_particles<false><<<(count + 255) / 256, 256, 0, st>>>(d, count, *k, steps, nullptr);
+    if (ev1) (void)hipEventRecord((hipEvent_t)ev1, st);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_particles_counted(Particle* d, int count, const bhrt_particle_k* k,
+                                             int steps, int* d_block_active, void* stream,
+                                             void* ev0, void* ev1) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ev0) (void)hipEventRecord((hipEvent_t)ev0, st);
+    if (count > 0 && steps > 0)
+        k_update_particles<true><<<(count + 255) / 256, 256, 0, st>>>(d, count, *k, steps,
+                                                                      d_block_active);
+    if (ev1) (void)hipEventRecord((hipEvent_t)ev1, st);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_particles_count(const Particle* d, int count, int* d_block_active,
+                                           void* stream) {
+    if (count > 0)
+        k_particles_count<<<(count + 255) / 256, 256, 0, (hipStream_t)stream>>>(d, count,
+                                                                                d_block_active);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_particles_scan(const int* d_block_active, int nblocks, int* d_offsets,
+                                          void* stream, void* ev0, void* ev1) {
+    hipStream_t st = (hipStream_t)stream;
+    if (ev0) (void)hipEventRecord((hipEvent_t)ev0, st);
+    if (nblocks > 0) k_particles_scan<<<1, 256, 0, st>>>(d_block_active, nblocks, d_offsets);
+    if (ev1) (void)hipEventRecord((hipEvent_t)ev1, st);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bhrt_launch_particles_scatter(const Particle* d, int count, const int* d_offsets,
+                                             int max_count, const bhrt_particle_data* out,
+                                             void* stream, void* ev0, void* ev1) {
+    hipStream_t st = (hipStream_t)stream;
+    const int nblocks = (count + 255) / 256;
+    if (ev0) (void)hipEventRecord((hipEvent_t)ev0, st);
+    if (count > 0)
+        k_particles_scatter<<<nblocks, 256, 0, st>>>(d, count, d_offsets, nblocks, max_count, *out);
     if (ev1) (void)hipEventRecord((hipEvent_t)ev1, st);
     return (int)hipGetLastError();
 }
