@@ -664,7 +664,7 @@ int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hi
 int bhrt_check_shift_chain(const double* in, int n, int site, double* out, void* hip_stream);
 
 /* Diagnostic: a guard of the trace loop that is decided from the high words of its f64 operands
- * (geodesic.hip BHRT_GUARD_WORDS), beside the exact test it filters for, on n cases of DEVICE
+ * (geodesic.hip all_below_2), beside the exact test it filters for, on n cases of DEVICE
  * arrays. kind 0 (the one guard built): the plain-value test of a stage's three accelerations,
  * a[3n] (b is not read and may be NULL). d_out[2i] = 1 where the high-word filter keeps the case
  * on the straight-line path, d_out[2i+1] = 1 where the exact test (every |a| <= 10) passes; the

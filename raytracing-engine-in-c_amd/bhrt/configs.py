@@ -127,10 +127,9 @@ class Config:
                          f"aspect and field of view) in {n} shards")
 
     def display_fields(self):
-        """The device fields of the visualizer's display call: rgba8 alone where the trace
-        kernel writes the colour at each ray's exit (bhrt_kernel.h BHRT_COLOUR_IN_TRACE: a disk
-        scene traced with RKF45, or with RK4 at a != 0: C3, C4), else also result and the hit
-        point that the separate colour pass reads (bhrt_api.c colour_args_bad)."""
+        """The device fields requested by the display call that bench.py's display leg is
+        measured with, exactly these: rgba8 alone for a disk scene traced with RKF45 or at
+        a != 0 (C3, C4), else rgba8 with result and the hit point."""
         fused = self.disk and (self.method == abi.INTEGRATOR_RKF45 or self.spin != 0.0)
         return ("rgba8",) if fused else ("result", "hit_x", "hit_y", "rgba8")
 

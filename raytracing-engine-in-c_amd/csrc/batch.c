@@ -278,16 +278,13 @@ static int trace_hits_pipelined(const Ray* rays, int n, const BlackHoleParams* b
             }
             HIP_TRY(hipEventRecord(c->chunk_done[k], st));
             if (mk & 4) HIP_TRY(hipEventRecord(c->tev[k][2], st));
-            /* chunk k's download is issued after chunk k + 1's upload (late = 1): both copy
-             * directions can share one in-order DMA queue, and a download queued there waits for
-             * its chunk's trace -- an upload issued behind it waited too, so chunk k + 1 could
-             * not start before chunk k had ended and the two trace streams ran one after the
-             * other (the 140 vs 205 Mrays/s "fresh-process mode" of VERDICT r5, DESIGN.md
-             * section 4). BHRT_BATCH_LATE_D2H=0: the round-5 order (A/B). */
-            const int late = bhrt_env_int("BHRT_BATCH_LATE_D2H", 1) != 0;
-            if (!late || k > 0)
-                if (batch_download(jobs, off, late ? k - 1 : k, d, mk)) return -1;
-            if (late && k == K - 1 && batch_download(jobs, off, k, d, mk)) return -1;
+            /* chunk k's download is issued after chunk k + 1's upload: both copy directions can
+             * share one in-order DMA queue, and a download queued there waits for its chunk's
+             * trace -- an upload issued behind it waited too, so chunk k + 1 could not start
+             * before chunk k had ended and the two trace streams ran one after the other (the
+             * 140 vs 205 Mrays/s "fresh-process mode" of VERDICT r5). */
+            if (k > 0 && batch_download(jobs, off, k - 1, d, mk)) return -1;
+            if (k == K - 1 && batch_download(jobs, off, k, d, mk)) return -1;
         }
     clock_gettime(CLOCK_MONOTONIC, &tt[1]);
     double wait_ms = 0.0, pack_ms = 0.0;

@@ -80,20 +80,13 @@ typedef struct {
 } bhrt_camera_k;
 
 /* Whether the trace kernel writes a scene's colour outputs at each ray's exit, from the state in
- * registers (no separate colour pass re-reading the hits). Since round 6 every scene: the
- * separate pass of a frame could only start once the trace kernel's last wave had ended, by
- * when the next frame's persistent workgroups held every wave slot, so a C2 frame's colour
- * landed ~1 frame late (k_colour dispatches averaged 5.5 ms), and on the
- * current kernels fusing costs nothing (C2 284.5 vs 284.6 Mrays/s same box,
- * profiles/r06/ab_fused_colour.txt; C5 +16%, C1 +9%). Scenes without a disk get the sky / horizon colour
- * alone (geodesic.hip colour_sky). BHRT_FUSE_ALL=0 builds round 5's rule (disk scenes with
- * RKF45 or a != 0; C3, C4) and BHRT_FUSE_COLOUR=0 at run time takes the separate pass (A/B). */
-#ifndef BHRT_FUSE_ALL
-#define BHRT_FUSE_ALL 1
-#endif
-#define BHRT_COLOUR_IN_TRACE(method, has_disk, spin)                                        \
-    (BHRT_FUSE_ALL ||                                                                       \
-     ((has_disk) && ((method) == INTEGRATOR_RKF45 || ((method) == INTEGRATOR_RK4 && (spin)))))
+ * registers (no separate colour pass re-reading the hits). Every scene does: the separate pass
+ * of a frame could only start once the trace kernel's last wave had ended, by when the next
+ * frame's persistent workgroups held every wave slot, so a C2 frame's colour landed ~1 frame
+ * late (k_colour dispatches averaged 5.5 ms), and fusing costs nothing (C2 284.5 vs 284.6
+ * Mrays/s same box, profiles/r06/ab_fused_colour.txt; C5 +16%, C1 +9%). Scenes without a disk
+ * get the sky / horizon colour alone (geodesic.hip colour_sky). BHRT_FUSE_COLOUR=0 at run time
+ * takes the separate pass (A/B, and the tests' reference path). */
 
 typedef struct {
     bhrt_scene_k sc;

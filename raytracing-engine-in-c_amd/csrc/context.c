@@ -415,9 +415,7 @@ int bhrt_ctx_launch_fn(devctx_t* c, bhrt_kparams* kp, hipStream_t stream, bhrt_l
     }
     /* the redo list follows the initial-state table (one extra field of the allocation) */
     if (kp->init) kp->redo = (int*)(kp->init + (size_t)BHRT_INIT_FIELDS * (size_t)kp->n);
-    if (c->npend == BHRT_RING &&
-        harvest(c, 1, stream, bhrt_env_int("BHRT_HARVEST_ALL", 0) ? BHRT_RING : BHRT_RING / 2) != 0)
-        return -1;
+    if (c->npend == BHRT_RING && harvest(c, 1, stream, BHRT_RING / 2) != 0) return -1;
     if (ring_order(c, stream)) return -1;
     int slot = c->next_slot;
     c->next_slot = (c->next_slot + 1) % BHRT_RING;
@@ -425,11 +423,6 @@ int bhrt_ctx_launch_fn(devctx_t* c, bhrt_kparams* kp, hipStream_t stream, bhrt_l
     kp->qhead = kp->ctl + BHRT_QHEAD_OFF;
     kp->diag_slot = slot;
     /* (the slot was zeroed when it was last harvested, or at the context's creation) */
-    if (bhrt_env_int("BHRT_LAUNCH_MEMSET", 0))  /* A/B: the per-launch fill kernel of round 4 */
-        HIP_TRY(hipMemsetAsync(kp->ctl, 0,
-                               (BHRT_QHEAD_OFF + ((size_t)kp->queue_stride << kp->queue_bits)) *
-                                   sizeof(unsigned long long),
-                               stream));
     if (!c->span_on) {
         HIP_TRY(hipEventRecord(c->span_ref, stream));
         c->span_on = 1;

@@ -122,13 +122,9 @@ __device__ __forceinline__ double max_abs_raw(double a, double b) {
 // Only forms that SAVE INSTRUCTIONS are built: a 32-bit compare of one high word issues no
 // faster than the f64 compare it would replace (4 cycles either way beside an f64 stream, at 1
 // and at 4 waves per SIMD: tools/probe/cmp_probe.hip, profiles/guardwords/cmp_probe.txt).
-// BHRT_GUARD_WORDS = 1: the filter in the RK4 stage pairs (rhs_given: C2 +1.3%, C1 +1.9% same-box);
-// 2: in the single-stage form (rhs) too, which RKF45 runs -- C3 -3.6% same-box, its kernel gains
-// scratch (profiles/guardwords/ab_parent_vs_new.txt), so that is not the default; 0: every
-// guard is the exact f64 test alone, the kernels of the commit before.
-#ifndef BHRT_GUARD_WORDS
-#define BHRT_GUARD_WORDS 1
-#endif
+// The filter is in the RK4 stage pairs (rhs_given: C2 +1.3%, C1 +1.9% same-box), not in the
+// single-stage form (rhs), which RKF45 runs: there it lost 3.6% on C3 same-box, its kernel
+// gaining scratch (profiles/guardwords/ab_parent_vs_new.txt).
 // the high word of x: a sub-register read, no instruction
 __device__ __forceinline__ unsigned hiword(double x) {
     return (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 32);
@@ -304,12 +300,6 @@ __device__ __forceinline__ void shift_or_eval(double a, double s0, double c0, do
 // A lane with !(|eps| <= bound) -- NaN included -- redoes the shift with shift_or_eval from the
 // same anchor, whose wide and direct forms treat every operand as before. Per lane, so a ray's
 // rounding never depends on its wave-mates. Returns whether the lane kept the short form.
-// BHRT_SHIFT_CHAIN: 1 both chained sites; 2 the wider alternative of that A/B (the advance alone,
-// two coefficients on 1/64, which no lane of any replayed frame exceeds); 0 every shift from
-// the iteration's start.
-#ifndef BHRT_SHIFT_CHAIN
-#define BHRT_SHIFT_CHAIN 1
-#endif
 template <int NC>
 __device__ __forceinline__ bool shift_chain(double a, double s0, double c0, double x, double& s,
                                             double& c, Counters* hc) {
@@ -396,7 +386,7 @@ __device__ __forceinline__ void repair_clamp(double (&d)[6]) {
 // where it is tested, rc < 1e150, of this stage and of the one it shares the reciprocal with.
 // A lane that fails it, or whose result is not a plain |d| <= 10 value, recomputes the stage in
 // the literal form (its own reciprocals) before the repair and clamps.
-template <bool HUGE, bool WORDS = BHRT_GUARD_WORDS != 0>
+template <bool HUGE, bool WORDS>
 __device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6], const Scene& sc,
                                            double st, double ct, double rc, double w2, bool ok) {
     // The factor -2 of d4 and d5 rides on the reciprocal (w2 = -2 / (r sin theta), rcp_nr_m2):
@@ -440,8 +430,7 @@ __device__ __forceinline__ void accel_fast(const double (&y)[6], double (&d)[6],
 #endif
 template <bool SPIN0, bool FAR, bool HUGE>
 __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const Scene& sc,
-                                    bool far_ok, Counters& n, Trig1& tr, bool first,
-                                    Trig1* keep = nullptr) {
+                                    bool far_ok, Counters& n, Trig1& tr, bool first) {
     d[0] = y[3];
     d[1] = y[4];
     d[2] = y[5];
@@ -459,8 +448,6 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
             ct = tr.c;
         } else {
             shift_or_eval(tr.a, tr.s, tr.c, y[1], st, ct, HUGE ? nullptr : &n);
-            // (rk4_step's stage 4: the anchor the advance of state[1] is chained from)
-            if (keep) *keep = Trig1{y[1], st, ct};
         }
         if ((FAR && HUGE) || BHRT_COUNT_STAGES) n.full++;
         // Fast form, straight-line: the same three accelerations with the divisions as one
@@ -480,7 +467,8 @@ __device__ __forceinline__ void rhs(const double (&y)[6], double (&d)[6], const 
         // derivative is the clamped |d3| <= 10 (or 0), so |state[0]| <= 0.1 * 20 * steps^2;
         // k_path (a caller-given t) and the HUGE redo keep it
         const bool ok = (!HUGE ? true : rc < 1.0e150) & (fabs(st) >= 0.01);
-        accel_fast<HUGE, BHRT_GUARD_WORDS == 2>(y, d, sc, st, ct, rc, rcp_nr_m2(rc * st), ok);
+        // (no high-word filter here: it lost 3.6% on C3, see all_below_2)
+        accel_fast<HUGE, false>(y, d, sc, st, ct, rc, rcp_nr_m2(rc * st), ok);
         return;
     }
     // :131-138
@@ -574,11 +562,14 @@ __device__ __forceinline__ double rkf45_sum5(double k1, double k3, double k4, do
     return kD1 * k1 + kD3 * k3 + kD4 * k4 + kD5 * k5 + kD6 * k6;
 }
 
-// One reciprocal for two a = 0 stages. In RK4 the position part of
-// stage 3's state is y + h/2 * (stage 2's velocities), and those are part of stage 2's STATE,
-// known before stage 2's accelerations are: both stages' x = rc sin theta exist right after
-// stage 1, and w = -2 / (x_a x_b) gives -2 / x_a = x_b w and -2 / x_b = x_a w: one v_rcp_f64 and
-// its refinement (7 issue slots) less for three products. Against the single form's
+// One reciprocal for two a = 0 stages. x = rc sin theta of a stage needs
+// only the position part (components 0, 1) of its state. In RK4 stage 2's is y + h/2 y[3..4],
+// known before any acceleration, so x1 and x2 both exist at the top of the iteration; stage 4's
+// is y + h (y[3..4] + h/2 k2[3..4]) -- stage 3's velocities, which need stage 2's accelerations
+// and nothing of stage 3 -- so x3 and x4 both exist once stage 2 is done. Pairs (1,2) and (3,4):
+// w = -2 / (x_a x_b) gives -2 / x_a = x_b w and -2 / x_b = x_a w, one v_rcp_f64 and its
+// refinement (7 issue slots) less for three products -- two reciprocals per iteration instead
+// of four, no loop-carried register added. Against the single form's
 // yr = st RN(1 / RN(rc st)) a member's yr = st RN(x_b RN(1 / RN(x_a x_b))) carries one rounding
 // more (x_b's own rounding cancels): five roundings, <= 6 ulp of 1 / rc with the reciprocal's
 // own taken as <= 1 ulp (measured worst: profiles/stagepairs/test_figures.txt).
@@ -589,16 +580,6 @@ __device__ __forceinline__ double rkf45_sum5(double k1, double k3, double k4, do
 // BOTH, and both stages take the literal form with their own reciprocals (accel_fast): a stage
 // never uses a quotient derived from an out-of-range partner. (An Inf, which no sine is, passes
 // the test and turns both members' quotients into NaN, which fail the plain-value test.)
-// The same holds one step further (BHRT_PAIR_RCP = 2, the default): x of a stage needs only the
-// position part (components 0, 1) of its state. Stage 2's is y + h/2 y[3..4], known before any
-// acceleration, so x1 and x2 both exist at the top of the iteration; stage 4's is
-// y + h (y[3..4] + h/2 k2[3..4]) -- stage 3's velocities, which need stage 2's accelerations and
-// nothing of stage 3 -- so x3 and x4 both exist once stage 2 is done. Pairs (1,2) and (3,4):
-// two reciprocals per iteration instead of three, no loop-carried register added, and every
-// stage (not two of the four) carries the pair's <= 6 ulp quotient bound.
-#ifndef BHRT_PAIR_RCP /* RK4 a = 0 stages sharing a reciprocal: 2: (1,2) and (3,4); 1: (2,3); 0: none */
-#define BHRT_PAIR_RCP 2
-#endif
 struct StageOps {
     double st, ct, rc, x;  // sin, cos of the stage's theta, its clamped r, x = rc * st (far: 1)
     bool ok;
@@ -647,36 +628,32 @@ __device__ __forceinline__ void rhs_given(const double (&y)[6], double (&d)[6], 
         return;
     }
     if ((FAR && HUGE) || BHRT_COUNT_STAGES) n.full++;
-    accel_fast<HUGE>(y, d, sc, o.st, o.ct, o.rc, w2, ok);
+    accel_fast<HUGE, true>(y, d, sc, o.st, o.ct, o.rc, w2, ok);
 }
 
 // rk4_integrate (math_util.c:162-207) on the six live components; the running sum
-// ((k1 + 2k2) + 2k3) + k4 is the reference's left-to-right evaluation order.
+// ((k1 + 2k2) + 2k3) + k4 is the reference's left-to-right evaluation order. Two forms: the
+// a = 0 step (SPIN0) with its paired reciprocals and chained shifts, and the generic step.
 template <bool SPIN0, bool FAR, bool HUGE, bool HS = false>
 __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, const Scene& sc,
                                          bool far_ok, Counters& n, Trig1& tr,
                                          const double* zs = nullptr) {
-    constexpr bool Z = zero_accel<SPIN0, FAR>();
-    // the a = 0 stages' chained anchors (shift_chain): stage 3's theta from stage 2's (CHAIN3),
-    // and t4, stage 4's theta with its sin, cos, handed back in tr for the caller's advance of
-    // state[1] (a stage 2 or 4 on the far-field branch takes no sin, cos: the anchor then
-    // stays tr)
-    constexpr bool CHAIN = SPIN0 && BHRT_SHIFT_CHAIN != 0;
-    constexpr bool CHAIN3 = SPIN0 && BHRT_SHIFT_CHAIN == 1;
     double k[6], acc[6], yt[6];
     const double hh = 0.5 * h;
-    Trig1 t4 = tr;
-    if constexpr (SPIN0 && BHRT_PAIR_RCP == 2) {
+    if constexpr (SPIN0) {
         // stages 1, 2 on one reciprocal and stages 3, 4 on another (pair_rcp). The position
         // parts formed ahead are the very expressions the stage-state loops would form
         // (k[0..1] of a stage are its state's [3..4]).
+        // Chained anchors (shift_chain): stage 3's theta from stage 2's (an), and t4, stage 4's
+        // theta with its sin, cos, handed back in tr for the caller's advance of state[1] (a
+        // stage 2 or 4 on the far-field branch takes no sin, cos: the anchor then stays tr)
         const double y20 = y[0] + hh * y[3], y21 = y[1] + hh * y[4];
         const bool far1 = FAR && far_ok && y[0] > sc.rs_x15;
         const bool far2 = FAR && far_ok && y20 > sc.rs_x15;
         StageOps o1, o2, o3, o4;
         double w1 = 0.0, w2 = 0.0, w3 = 0.0, w4 = 0.0;
         bool ok = false;
-        Trig1 an = tr;
+        Trig1 an = tr, t4 = tr;
         if (!FAR || !(far1 & far2)) {
             o1.st = tr.s;  // carried from the previous iteration (ray_iterate)
             o1.ct = tr.c;
@@ -687,7 +664,7 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
                 o1.ok = true;
             }
             stage_ops<FAR, HUGE>(y20, y21, far2, sc, n, tr, o2);
-            if (CHAIN3) an = Trig1{y21, o2.st, o2.ct};
+            an = Trig1{y21, o2.st, o2.ct};
             ok = pair_rcp(o1, o2, w1, w2);
         }
         rhs_given<FAR, HUGE>(y, k, sc, far1, n, o1, w1, ok);
@@ -707,9 +684,9 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         const bool far4 = FAR && far_ok && y40 > sc.rs_x15;
         ok = false;
         if (!FAR || !(far3 & far4)) {
-            stage_ops<FAR, HUGE, CHAIN3 ? 2 : 0>(yt[0], yt[1], far3, sc, n, an, o3);
+            stage_ops<FAR, HUGE, 2>(yt[0], yt[1], far3, sc, n, an, o3);
             stage_ops<FAR, HUGE>(y40, y41, far4, sc, n, tr, o4);
-            if (CHAIN) t4 = Trig1{y41, o4.st, o4.ct};
+            t4 = Trig1{y41, o4.st, o4.ct};
             ok = pair_rcp(o3, o4, w3, w4);
         }
         rhs_given<FAR, HUGE>(yt, k, sc, far3, n, o3, w3, ok);
@@ -721,40 +698,17 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         rhs_given<FAR, HUGE>(yt, k, sc, far4, n, o4, w4, ok);
 #pragma unroll
         for (int i = 0; i < 6; i++) y[i] = __builtin_fma(h6, acc[i] + k[i], y[i]);
-        if (CHAIN) tr = t4;
-        return;
-    }
-    rhs<SPIN0, FAR, HUGE>(y, k, sc, far_ok, n, tr, true);
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        acc[i] = k[i];
-        yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
-    }
-    if constexpr (SPIN0 && BHRT_PAIR_RCP) {
-        // stages 2 and 3 on one reciprocal (pair_rcp). Stage 3's y0, y1 are the very expressions
-        // the stage-state loop below would form (k[0..1] of stage 2 are yt[3..4]).
-        const double y30 = y[0] + hh * yt[3], y31 = y[1] + hh * yt[4];
-        const bool far2 = FAR && far_ok && yt[0] > sc.rs_x15;
-        const bool far3 = FAR && far_ok && y30 > sc.rs_x15;
-        StageOps o2, o3;
-        double w2 = 0.0, w3 = 0.0;
-        bool ok = false;
-        if (!FAR || !(far2 & far3)) {
-            stage_ops<FAR, HUGE>(yt[0], yt[1], far2, sc, n, tr, o2);
-            if constexpr (CHAIN3)
-                stage_ops<FAR, HUGE, 2>(y30, y31, far3, sc, n, Trig1{yt[1], o2.st, o2.ct}, o3);
-            else
-                stage_ops<FAR, HUGE>(y30, y31, far3, sc, n, tr, o3);
-            ok = pair_rcp(o2, o3, w2, w3);
-        }
-        rhs_given<FAR, HUGE>(yt, k, sc, far2, n, o2, w2, ok);
+        tr = t4;
+    } else {
+        // Z: components 3..5 carried unchanged (zero_accel); HS: zs holds the hoisted stage sums
+        // of components 0..2 (hoist_sums)
+        constexpr bool Z = zero_accel<SPIN0, FAR>();
+        rhs<SPIN0, FAR, HUGE>(y, k, sc, far_ok, n, tr, true);
 #pragma unroll
         for (int i = 0; i < 6; i++) {
-            acc[i] = rk4_acc(acc[i], k[i]);
-            yt[i] = i == 0 ? y30 : i == 1 ? y31 : y[i] + hh * k[i];
+            acc[i] = k[i];
+            yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
         }
-        rhs_given<FAR, HUGE>(yt, k, sc, far3, n, o3, w3, ok);
-    } else {
         rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
 #pragma unroll
         for (int i = 0; i < 6; i++) {
@@ -762,25 +716,22 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
             yt[i] = (Z && i >= 3) ? y[i] : y[i] + hh * k[i];
         }
         rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
-    }
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        acc[i] = rk4_acc(acc[i], k[i]);
-        yt[i] = (Z && i >= 3) ? y[i] : y[i] + h * k[i];
-    }
-    // (BHRT_PAIR_RCP = 1 or 0 with the chained advance: stage 4 leaves its anchor in t4; with 0
-    // stage 3 keeps its shift from tr)
-    rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false, CHAIN ? &t4 : nullptr);
+        for (int i = 0; i < 6; i++) {
+            acc[i] = rk4_acc(acc[i], k[i]);
+            yt[i] = (Z && i >= 3) ? y[i] : y[i] + h * k[i];
+        }
+        rhs<SPIN0, FAR, HUGE>(yt, k, sc, far_ok, n, tr, false);
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        // h * (...) / 6 as (h * RN(1/6)) * (...), h6 = h * RN(1/6) (the caller's): the increment
-        // differs by <= 1 ulp of itself, which is ~h*|k| / |y| ulp of the state
-        if (HS && i < 3)
-            y[i] = __builtin_fma(h6, zs[i], y[i]);
-        else if (!(Z && i >= 3))
-            y[i] = __builtin_fma(h6, acc[i] + k[i], y[i]);
+        for (int i = 0; i < 6; i++) {
+            // h * (...) / 6 as (h * RN(1/6)) * (...), h6 = h * RN(1/6) (the caller's): the
+            // increment differs by <= 1 ulp of itself, which is ~h*|k| / |y| ulp of the state
+            if (HS && i < 3)
+                y[i] = __builtin_fma(h6, zs[i], y[i]);
+            else if (!(Z && i >= 3))
+                y[i] = __builtin_fma(h6, acc[i] + k[i], y[i]);
+        }
     }
-    if (CHAIN) tr = t4;
 }
 
 // RKF45's accept test (math_util.c:367-391, 402-434): accept iff
@@ -1421,13 +1372,12 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
         // sin, cos of state[1] feed only the a = 0 accelerations (rhs); the Kerr branch
         // (a != 0, accelerations 0) never reads them, and the compiler keeps a dead
         // loop-carried advance alive otherwise (C5: 45 instructions of the loop)
-        if constexpr (SPIN0 && METHOD == INTEGRATOR_RK4 && BHRT_SHIFT_CHAIN) {
+        if constexpr (SPIN0 && METHOD == INTEGRATOR_RK4) {
             // from stage 4's theta, sin, cos (rk4_step left them in tr), a second-order distance
-            // away: one coefficient (shift_chain; two with BHRT_SHIFT_CHAIN = 2). The carried
-            // pair now passes through two shifts per iteration, stage 4's and this one
-            // (DESIGN.md §2.3).
+            // away: one coefficient (shift_chain). The carried pair passes through two shifts
+            // per iteration, stage 4's and this one.
             double s1, c1;
-            shift_chain<BHRT_SHIFT_CHAIN == 1 ? 1 : 2>(tr.a, tr.s, tr.c, R.y[1], s1, c1, hc);
+            shift_chain<1>(tr.a, tr.s, tr.c, R.y[1], s1, c1, hc);
             R.s1 = s1;
             R.c1 = c1;
         } else if (SPIN0) {
@@ -1721,26 +1671,12 @@ __device__ __forceinline__ void store_colour(const bhrt_frame_soa& s, int i, dou
     }
 }
 
-// store_hit, and where the scene's colour is written in the trace kernel
-// (BHRT_COLOUR_IN_TRACE, bhrt_kernel.h; colour_fused) the colour outputs from the exit state in
-// registers. Other instantiations do not contain the colour code at all (its registers cost
-// more in the loop than the separate pass does).
+// store_hit, and unless the launch takes the separate colour pass (colour_fused, bhrt_kernel.h)
+// the colour outputs from the exit state in registers.
 // The launch parameters as an opaque pointer into the kernel argument segment: the fields read
 // through it are loaded (scalar loads) where they are used, instead of being kept live across
 // the persistent loop. The refill's camera constants and the store's output pointers held that
 // way overflowed the 106 SGPRs into VGPR lanes (v_readlane in every block of the loop).
-#ifndef BHRT_COLD_KP
-#define BHRT_COLD_KP 1
-#endif
-#ifndef BHRT_UNIFORM_TRIP  /* 1: every instantiation; 0: none; default: RK4 a = 0 (uniform_trip) */
-#define BHRT_UNIFORM_TRIP 2
-#endif
-#ifndef BHRT_DEFER_STORE
-#define BHRT_DEFER_STORE 1
-#endif
-#ifndef BHRT_FRAME_STAMPS  /* the launch's execution window in ctl[8..10] (bhrt_stats.frame_ms) */
-#define BHRT_FRAME_STAMPS 1
-#endif
 typedef const __attribute__((address_space(4))) bhrt_kparams kparams_as4;
 // (k_trace's only argument: it starts the kernel argument segment)
 __device__ __forceinline__ const bhrt_kparams& cold(const bhrt_kparams&) {
@@ -1749,10 +1685,9 @@ __device__ __forceinline__ const bhrt_kparams& cold(const bhrt_kparams&) {
     return *(const bhrt_kparams*)p;
 }
 
-template <int METHOD, bool DISK, bool SPIN0>
+template <bool DISK>
 __device__ __forceinline__ void store_ray(const bhrt_kparams& kp, int i, const Ray_& R, int term) {
     store_hit(kp.out, i, R, term, kp.sc);
-    if (!BHRT_COLOUR_IN_TRACE(METHOD, DISK, !SPIN0)) return;
     if (kp.colour_fused && (kp.out.rgb_r || kp.out.rgba32f || kp.out.rgba8)) {
         const int res = term == T_DISK ? RAY_DISK : (term == T_HORIZON ? RAY_HORIZON : RAY_MAX_STEPS);
         double r, g, b;
@@ -1880,13 +1815,10 @@ template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, int INL>
 constexpr bool c3_camera() {
     return METHOD == INTEGRATOR_RKF45 && DISK && SPIN0 && !FAR && !HUGE && INL == 1;
 }
-// the accept-all attempts (ACC, C5): BHRT_ACC_WAVES per SIMD
-#ifndef BHRT_ACC_WAVES
-#define BHRT_ACC_WAVES 4
-#endif
+// the accept-all attempts (ACC, C5): 4 per SIMD
 template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, int INL, bool ACC = false>
 constexpr int trace_waves_k() {
-    return ACC ? BHRT_ACC_WAVES
+    return ACC ? 4
          : c3_camera<METHOD, DISK, SPIN0, FAR, HUGE, INL>() ? 3 : trace_waves<METHOD, DISK, SPIN0>();
 }
 // Waves per SIMD ONE hot launch takes (0: every resident slot). C3 is resident at 3 waves per
@@ -1897,12 +1829,10 @@ constexpr int trace_waves_k() {
 // The accept-all kernel (C5) launches 3 of its 4 resident waves per SIMD: +0.5...2.5% same-box
 // over three sessions at 16 attempts per trip (2, 2.5 and 3.5 waves per SIMD alike, C4 -2% at 3;
 // profiles/r06/ab_kernel_knobs.txt).
-#ifndef BHRT_ACC_LAUNCH_WAVES
-#define BHRT_ACC_LAUNCH_WAVES 3
-#endif
 template <int METHOD, bool DISK, bool SPIN0, bool FAR, int INL, bool ACC = false>
 constexpr int trace_launch_waves() {
-    return c3_camera<METHOD, DISK, SPIN0, FAR, false, INL>() ? 2 : ACC ? BHRT_ACC_LAUNCH_WAVES : 0;}
+    return c3_camera<METHOD, DISK, SPIN0, FAR, false, INL>() ? 2 : ACC ? 3 : 0;
+}
 constexpr int BHRT_TRACE_WAVES_PER_BLOCK = 4;
 
 // Ray queues of k_trace: 64-id block b of the launch belongs to queue b mod 2^qbits; queue q's
@@ -1937,12 +1867,7 @@ __device__ unsigned long long g_stamps[kStampSlots * kStampWaves * kStampWords];
 // pay the trip's own cost (the live ballot, the refill test and its scalar loads) for fewer
 // instructions each: 16 per trip, C4 +2.2%, C5 +14.5% same-box against 6 / 2; the sweeps
 // flatten from 12 (C5) / 16 (C4) up to 24 / 32 (profiles/r06/ab_unroll.txt).
-#ifndef BHRT_UNROLL_ZA
-#define BHRT_UNROLL_ZA 16
-#endif
-#ifndef BHRT_UNROLL_A0
-#define BHRT_UNROLL_A0 4
-#endif
+constexpr int kUnrollZA = 16, kUnrollA0 = 4;
 // The trip's later iterations under a wave-uniform guard (k_trace): RK4 a = 0 (C1, C2), whose
 // predicated form copies ~12 carried values (v_mov_b64) at the end of every iteration for the
 // lanes that stopped. 8 per trip gave C1 +1.2%, C2 +0.4% against the predicated 10 same-box (10
@@ -1951,8 +1876,16 @@ __device__ unsigned long long g_stamps[kStampSlots * kStampWaves * kStampWords];
 // C4 -1%, C5 +-0; profiles/r06/ab_unroll.txt).
 template <int METHOD, bool SPIN0>
 constexpr bool uniform_trip() {
-    return BHRT_UNIFORM_TRIP == 1 ||
-           (BHRT_UNIFORM_TRIP == 2 && METHOD == INTEGRATOR_RK4 && SPIN0);
+    return METHOD == INTEGRATOR_RK4 && SPIN0;
+}
+// Whether the instantiation deals its rays over several queues (k_trace). The RK4 a = 0 path
+// (C1, C2) keeps ONE queue and claims exactly the idle lanes: its rays live up to max_steps
+// iterations, so claims are rare (~30 M/s on C2) and the multi-queue refill block measured -2%
+// there (its registers perturb the 4-wave hot loop; same-box A/B,
+// profiles/r02_claim_sweep.txt).
+template <int METHOD, bool SPIN0>
+constexpr bool multi_queue() {
+    return !(METHOD == INTEGRATOR_RK4 && SPIN0);
 }
 // The exits of a wave-uniform trip as lane masks (ray_iterate MASK): the trip's guard needs only
 // "does any lane stop", so an iteration ORs the ballots of its three exit compares (SALU; a disk
@@ -1961,12 +1894,9 @@ constexpr bool uniform_trip() {
 // before -- is formed once, on the edge the trip leaves by (exit_term), from the same compares
 // of the same final values. RK4 disk instantiations only (every iteration moves, so there is no
 // fixed-point exit). The reference's exit order and every output are unchanged.
-#ifndef BHRT_EXIT_MASKS
-#define BHRT_EXIT_MASKS 1
-#endif
 template <int METHOD, bool DISK, bool SPIN0>
 constexpr bool exit_masks() {
-    return BHRT_EXIT_MASKS && uniform_trip<METHOD, SPIN0>() && DISK && METHOD == INTEGRATOR_RK4;
+    return uniform_trip<METHOD, SPIN0>() && DISK && METHOD == INTEGRATOR_RK4;
 }
 // the reference's exit order (disk, horizon, distance, step budget) after ray_iterate<MASK>,
 // T_NONE for a lane that goes on; takes the disk hit's mark off the step count
@@ -1981,8 +1911,8 @@ __device__ __forceinline__ int exit_term(Ray_& R, const Scene& sc) {
 template <int METHOD, bool SPIN0, bool FAR, bool HUGE, bool ACC = false>
 constexpr int unroll_n() {
     return HUGE                      ? 1
-         : METHOD == INTEGRATOR_RK4  ? (zero_accel<SPIN0, FAR>() ? BHRT_UNROLL_ZA : BHRT_UNROLL_A0)
-         : ACC                       ? BHRT_UNROLL_ZA
+         : METHOD == INTEGRATOR_RK4  ? (zero_accel<SPIN0, FAR>() ? kUnrollZA : kUnrollA0)
+         : ACC                       ? kUnrollZA
                                      : 2;
 }
 
@@ -2014,7 +1944,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     // complement of the start -- stamped by the first workgroup's first wave alone (workgroups
     // are dispatched in order; one atomic per wave at the launch's start would serialise 4096
     // atomics on one word) -- and ctl[9] the latest end
-    if (!HUGE && BHRT_FRAME_STAMPS && blockIdx.x == 0 && threadIdx.x == 0)
+    if (!HUGE && blockIdx.x == 0 && threadIdx.x == 0)
         atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
 #if BHRT_WAVE_STAMPS
     const unsigned long long st_t0 = (unsigned long long)wall_clock64();
@@ -2036,11 +1966,8 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     // at least claim_min, guided scheduling) that the wave hands out over its next refills.
     // Per-wave state in LDS (touched only at refill, so it holds no registers across the
     // loop): [lo, hi) = claimed ids not yet handed out, cur = queue, moves = queues left behind.
-    // The RK4 a = 0 path (C1, C2) keeps ONE queue and claims exactly the idle lanes: its rays
-    // live up to max_steps iterations, so claims are rare (~30 M/s on C2) and the multi-queue
-    // refill block measured -2% there (its registers perturb the 4-wave hot loop; same-box
-    // A/B, profiles/r02_claim_sweep.txt).
-    constexpr bool MULTIQ = !(METHOD == INTEGRATOR_RK4 && SPIN0);
+    // (The RK4 a = 0 path keeps one queue: multi_queue.)
+    constexpr bool MULTIQ = multi_queue<METHOD, SPIN0>();
     __shared__ unsigned s_q[BHRT_TRACE_WAVES_PER_BLOCK][4];
     const unsigned ntotal = (unsigned)total;
     const unsigned qbits = HUGE ? 0u : (unsigned)kp.queue_bits;
@@ -2056,20 +1983,19 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
         s_q[wv][2] = (blockIdx.x * (blockDim.x >> 6) + wv) & (nq - 1u);
         s_q[wv][3] = 0u;
     }
-    constexpr bool COLD = BHRT_COLD_KP;
     // Deferred stores (drained-refill instantiations): a ray that finishes keeps its final state
     // in its lane's registers (the lane takes no new ray before the wave's next refill) and is
     // stored AT that refill, together with every other lane that finished meanwhile -- where a
     // wave refills only once drained (C3, C4, C5), all 64 lanes store at once, full lines of
     // every field, instead of a few lanes per trip (partial lines, written to HBM more than once:
     // C3's traffic was 1.40x its output) -- and the trip loop has no store code in it.
-    constexpr bool DEFER = MULTIQ && !HUGE && BHRT_DEFER_STORE;
+    constexpr bool DEFER = MULTIQ && !HUGE;
     int pterm = T_NONE;  // DEFER: how this lane's finished ray ended (T_NONE: nothing pending)
     bool exhausted = false;  // no ids left to claim or hand out; wave-uniform
     const HSel hsel = hsel_of<hsel_vgpr<METHOD, DISK, SPIN0>()>(kp.sc);
     for (;;) {
         // (re-laundered at the top of every trip, in wave-uniform control flow)
-        const bhrt_kparams& kc = COLD ? cold(kp) : kp;
+        const bhrt_kparams& kc = cold(kp);
         const unsigned long long live_mask = __ballot(live);
         int n_live = __popcll(live_mask);
         if (!exhausted && (64 - n_live >= kp.refill || n_live == 0)) {
@@ -2077,7 +2003,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
             st_refills++;
 #endif
             if constexpr (DEFER) {
-                if (pterm != T_NONE) store_ray<METHOD, DISK, SPIN0>(kc, rid, R, pterm);
+                if (pterm != T_NONE) store_ray<DISK>(kc, rid, R, pterm);
                 pterm = T_NONE;
             }
             bool ok;
@@ -2214,7 +2140,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                     n.rays++;
                     live = true;
                     if (kp.sc.max_steps <= 0) {  // loop never runs: MAX_STEPS, steps 0
-                        store_ray<METHOD, DISK, SPIN0>(kc, rid, R, T_MAXSTEPS);
+                        store_ray<DISK>(kc, rid, R, T_MAXSTEPS);
                         live = false;
                         n.clear_huge();
                     }
@@ -2225,7 +2151,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
         if (n_live == 0) {
             if (exhausted) {
                 if constexpr (DEFER) {
-                    if (pterm != T_NONE) store_ray<METHOD, DISK, SPIN0>(kc, rid, R, pterm);
+                    if (pterm != T_NONE) store_ray<DISK>(kc, rid, R, pterm);
                 }
                 break;
             }
@@ -2283,7 +2209,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                 if constexpr (DEFER)
                     pterm = term;
                 else
-                    store_ray<METHOD, DISK, SPIN0>(kc, rid, R, term);
+                    store_ray<DISK>(kc, rid, R, term);
                 live = false;
             }
         }
@@ -2319,7 +2245,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     }
 #endif
     if (lane == 0) {
-        if (BHRT_FRAME_STAMPS) atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
+        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
         if (s0) atomicAdd(kp.ctl + 1, s0);
         if (s1) atomicAdd(kp.ctl + 2, s1);
         if (s2) atomicAdd(kp.ctl + 3, s2);
@@ -2351,10 +2277,8 @@ __global__ __launch_bounds__(256) void k_colour(const bhrt_kparams kp) {
                   res == RAY_DISK ? s.hit_y[i] : 0.0, dx, dy, dz, r, g, b);
         store_colour(s, i, r, g, b);
     }
-    if (BHRT_FRAME_STAMPS) {
-        __syncthreads();  // the frame is complete once the last workgroup's stores are (ctl[10])
-        if (threadIdx.x == 0) atomicMax(kp.ctl + 10, (unsigned long long)wall_clock64());
-    }
+    __syncthreads();  // the frame is complete once the last workgroup's stores are (ctl[10])
+    if (threadIdx.x == 0) atomicMax(kp.ctl + 10, (unsigned long long)wall_clock64());
 }
 
 // Supersampled frames (bhrt_kernel.h bhrt_ss_rays_k): the directions of one sample's rays, one
@@ -2682,20 +2606,10 @@ constexpr int kRingDoubles = BHRT_PATHS_RING * 3;
 constexpr int kRingStride = kRingDoubles + 1;  // odd: lanes' rings start on different LDS banks
 static_assert(kRingDoubles <= 32, "a half-wave writes one lane's ring");
 
-// Occupancy: BHRT_PATHS_WAVES > 0 compiles k_paths for that many waves per SIMD (the A/B knob
-// behind DESIGN.md section 12's table); 0 leaves the register budget to the compiler.
-#ifndef BHRT_PATHS_WAVES
-#define BHRT_PATHS_WAVES 0
-#endif
-#if BHRT_PATHS_WAVES > 0
-#define BHRT_PATHS_BOUNDS \
-    __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(BHRT_PATHS_WAVES)))
-#else
-#define BHRT_PATHS_BOUNDS __launch_bounds__(64)
-#endif
-
+// Occupancy: the register budget is the compiler's: compiled for 4 or 3 waves per SIMD the
+// direct form lost 6% on C2 and 13-14% on C4.
 template <int METHOD, bool DISK, bool SPIN0, bool STAGED>
-__global__ BHRT_PATHS_BOUNDS void k_paths(const bhrt_kparams kp, const bhrt_paths_k pk) {
+__global__ __launch_bounds__(64) void k_paths(const bhrt_kparams kp, const bhrt_paths_k pk) {
     __shared__ double ring[STAGED ? 64 * kRingStride : 1];
     const int lane = threadIdx.x;
     const size_t P = (size_t)pk.max_positions;
@@ -2703,8 +2617,7 @@ __global__ BHRT_PATHS_BOUNDS void k_paths(const bhrt_kparams kp, const bhrt_path
     double* const xyz = reinterpret_cast<double*>(pk.out.xyz);
     float* const xyz32 = pk.out.xyz32;
     const bool record = xyz != nullptr || xyz32 != nullptr;
-    if (BHRT_FRAME_STAMPS && lane == 0)
-        atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
     Counters n;
     const HSel hsel = hsel_of(kp.sc);
     for (;;) {
@@ -2818,7 +2731,7 @@ __global__ BHRT_PATHS_BOUNDS void k_paths(const bhrt_kparams kp, const bhrt_path
     const unsigned long long s0 = wave_sum(n.rays), s1 = wave_sum(n.iters), s2 = wave_sum(n.full),
                              s3 = wave_sum(n.far_), s4 = wave_sum(n.kerr);
     if (lane == 0) {
-        if (BHRT_FRAME_STAMPS) atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
+        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
         if (s0) atomicAdd(kp.ctl + 1, s0);
         if (s1) atomicAdd(kp.ctl + 2, s1);
         if (s2) atomicAdd(kp.ctl + 3, s2);
@@ -2925,7 +2838,7 @@ __global__ void k_check_shift_chain(const double* in, int n, int site, double* o
     out[5 * i + 4] = fast ? 1.0 : 0.0;
 }
 
-// A high-word guard (BHRT_GUARD_WORDS) beside the exact test it filters for, on given operands.
+// A high-word guard (all_below_2) beside the exact test it filters for, on given operands.
 // kind 0, the one guard built: accel_fast's plain-value test of a stage's three accelerations
 // a[3i..3i+2] (b is not read). out[2i] = the filter's answer (all_below_2), out[2i+1] = the exact
 // test's (every |a| <= 10, NaN failing).
@@ -3028,7 +2941,7 @@ void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
         cap = kp.grid_blocks < cap ? kp.grid_blocks : cap;
     } else if (kp.grid_div > 0) {
         cap = cap / kp.grid_div > 0 ? cap / kp.grid_div : 1;
-    } else if (!(METHOD == INTEGRATOR_RK4 && SPIN0) && kp.min_tiles > 0 &&  // (MULTIQ)
+    } else if (multi_queue<METHOD, SPIN0>() && kp.min_tiles > 0 &&
                (long)kp.n < 64L * kp.min_tiles * (long)cap * (lanes / 64)) {
         cap = (cap + 1) / 2;
     }

@@ -25,11 +25,11 @@ static int refill_default(const bhrt_scene_k* s) {
     return (s->method == INTEGRATOR_RK4 && s->spin0) ? 8 : 64;
 }
 
-/* Where the trace kernel writes the colour outputs at each ray's exit, from the state in
- * registers (bhrt_colour_in_trace), the separate pass's inputs -- result and hit point -- need
- * not exist on the device. BHRT_FUSE_COLOUR=0 keeps the separate colour pass (A/B). */
+/* The trace kernel writes the colour outputs at each ray's exit, from the state in registers
+ * (bhrt_kernel.h), so the separate pass's inputs -- result and hit point -- need not exist on
+ * the device. BHRT_FUSE_COLOUR=0 keeps the separate colour pass (A/B), for every scene alike. */
 int bhrt_colour_fused(int method, int has_disk, int spin) {
-    return BHRT_COLOUR_IN_TRACE(method, has_disk, spin) && bhrt_env_int("BHRT_FUSE_COLOUR", 1) != 0;
+    return bhrt_env_int("BHRT_FUSE_COLOUR", 1) != 0;
 }
 
 /* Ray queues of k_trace: 2^queue_bits queue heads, queue_stride words apart,

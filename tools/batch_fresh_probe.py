@@ -13,7 +13,7 @@ calls, then the mode's action, then more calls; per call the wall ms. Modes:
   batch_small  a 64-ray trace_rays_batch instead
   warm1        one drop-in trace_ray BEFORE the first batch call (what the first call's cost is)
   env:K=V,...  base with extra environment (e.g. env:BHRT_STREAM_QUEUE=0)
-  MODE@K=V,... a mode with extra environment (e.g. batch_small@BHRT_BATCH_LATE_D2H=0)
+  MODE@K=V,... a mode with extra environment (e.g. batch_small@BHRT_BATCH_STREAMS=1)
 """
 import os
 import subprocess

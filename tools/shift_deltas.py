@@ -10,7 +10,7 @@ ray_derivatives, raytracer.c:44-154; every ray run to its oracle step count) on 
 and reports, per site and threshold T, the fraction of lane evaluations beyond T and the fraction
 of 8x8-tile "waves" (a wave's 64 lanes = one claim tile) with any lane beyond T.
 
-Two more sites are the chained anchors (BHRT_SHIFT_CHAIN): stage 3 shifted from stage 2's angle
+Two more sites are the chained anchors (shift_chain): stage 3 shifted from stage 2's angle
 (theta3 - theta2 = h/2 (k2 - k1)[1]) and the advance of state[1] shifted from stage 4's angle
 (theta' - theta4); both differences are second order in h. Per site the largest |delta| of the
 frame is printed, and beside the tile count the mixed-wave model: a refilled wave holds rays of
@@ -19,8 +19,8 @@ fast path with probability 1 - (1 - p)^64, p the lane fraction beyond T. Where t
 1e-4 (marked "ok") a narrower polynomial on T costs no wave its branch; where it is not, measure
 (profiles/shiftchain/ab_parent_vs_new.txt: the views down the polar axis).
 
-The replay also counts what the high-word filter of the plain-value test (all_below_2,
-BHRT_GUARD_WORDS) holds back: lane-stages whose raw accelerations hold a |d| >= 2 or a non-finite
+The replay also counts what the high-word filter of the plain-value test (all_below_2)
+holds back: lane-stages whose raw accelerations hold a |d| >= 2 or a non-finite
 value -- they take the exact |d| <= 10 test in the rare block -- and, of those, the ones the exact
 test fails too (the literal form, as before), with the same tile and mixed-wave figures.
 
