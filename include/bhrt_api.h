@@ -221,6 +221,8 @@ typedef struct {
 
 /* Frame flags */
 #define BHRT_FLAG_DOPPLER 1 /* disk colour through apply_relativistic_effects (config C4) */
+#define BHRT_FLAG_SKY 2     /* non-disk, non-horizon rays take their colour from the calling
+                               thread's bound sky map ("Sky maps" below) instead of the gradient */
 
 /* Structure-of-arrays frame. Element i is the i-th ray of the launch (for a camera frame:
  * the i-th pixel of the shard, row-major over the shard's rows). Any pointer may be NULL,
@@ -788,6 +790,78 @@ void bhrt_particles_destroy(bhrt_particles* ps);
 int  bhrt_particles_kernel_ms(bhrt_particles* ps, const BlackHoleParams* blackhole,
                               const SimulationConfig* config, int max_count,
                               const bhrt_particle_data* device_out, double ms[5]);
+
+/* ---- Sky maps: an environment texture looked up where a ray leaves the scene ----
+ * trace_pixel's two-colour background is a stand-in ("In a real implementation, this would be a
+ * texture lookup", raytracer.c:1146-1157). With BHRT_FLAG_SKY a frame takes the colour of every
+ * ray that is neither a disk hit nor a horizon ray from a caller's map instead.
+ *
+ * THE RULE (tests/sky_rule.py restates it in numpy).
+ *  The map.    Equirectangular, W x H texels T[j][i][0..2] stored as float32. Row j = 0 touches
+ *              theta = 0, the +z axis (the pole of cartesian_to_spherical, spacetime.c:201);
+ *              column 0 starts at phi = -pi; texel centres lie at (i + 0.5, j + 0.5). Input formats:
+ *              BHRT_SKY_RGB32F, [H][W][3] float; BHRT_SKY_RGBA8, [H][W][4] bytes, the texel
+ *              (float)b / 255.0f, alpha ignored.
+ *  The lookup  of a vector d, all of it IEEE double with no contraction:
+ *              1. L = sqrt((dx dx + dy dy) + dz dz); a d whose L is not a finite value > 0 (a zero
+ *                 or NaN vector, an overflowed sum) gives black, (0, 0, 0);
+ *              2. theta = acos(clamp(dz / L, -1, 1));  3. phi = atan2(dy, dx);
+ *              4. fx = (phi + pi) (W / (2 pi)) - 0.5, fy = theta (H / pi) - 0.5, the two factors
+ *                 formed once, at bhrt_sky_create;
+ *              5. i0 = floor(fx), wx = fx - i0, j0 = floor(fy), wy = fy - j0;
+ *              6. columns wrap, i0 mod W and (i0 + 1) mod W; rows j0 and j0 + 1 clamp to [0, H - 1];
+ *              7. c = (T00 (1 - wx) + T01 wx) (1 - wy) + (T10 (1 - wx) + T11 wx) wy per channel, on
+ *                 (double) texels.
+ *              Bilinear only: continuous across texel borders, the seam and the poles, so a
+ *              last-digit difference in acos / atan2 moves the colour by a last digit. acos and
+ *              atan2 are the device library's; the tests hold them to 1e-9 of the colour.
+ *  Which d.    A RAY_MAX_DISTANCE ray -- the only class that has left the scene -- takes its EXIT
+ *              CHORD d = p_k - p_(k-1), the two path points of the iteration that ended it (the
+ *              last segment bhrt_trace_paths draws; RayTraceHit.sky_direction is unpinned for RK4
+ *              and reads spherical components as Cartesian ones). A chord with a component that is
+ *              not finite, or whose squared length (dx dx + dy dy) + dz dz is not > 0, does not
+ *              count. That ray, and every other class but disk and horizon (RAY_MAX_STEPS: the
+ *              step budget, a stuck RKF45 ray, max_integration_steps == 0, the no-op integrators),
+ *              takes the direction the gradient reads: the ray's own initial direction.
+ *              Disk and horizon colours are unchanged, and so is BHRT_FLAG_DOPPLER.
+ *  The flag.   A frame uses the map only when flags has BHRT_FLAG_SKY AND a map is bound on the
+ *              calling thread (bhrt_set_sky). The flag with no map bound returns -1. A bound map
+ *              with no flag changes nothing: without the flag every call gives the bits it gave
+ *              before. The flag travels with `flags` into every call that writes colour:
+ *              bhrt_render_frame_device, bhrt_trace_rays_device and their host forms,
+ *              bhrt_render_frame_ss*, bhrt_render_frame_adaptive*, bhrt_accum_frame*. The drop-in
+ *              symbols have no flags argument and are unchanged.
+ *  Devices.    A map lives on the device that was current at bhrt_sky_create. A call that would
+ *              launch on another device returns -1 before any launch: the multi-GPU split of the
+ *              host forms and bhrt_render_frame_gather included (one map per device is not
+ *              offered).
+ *  Refusals.   -1 with bhrt_last_error set and nothing written, each decided BEFORE ANY HIP CALL
+ *              (the current device's query aside): a NULL argument; width or height < 1;
+ *              width * height > 2^26; an unknown format; a float texel that is not finite; n < 1
+ *              for the lookups; a current device other than the map's. HIP failures also return -1.
+ *  Lifetime.   The map must outlive every frame queued with it; bhrt_sky_destroy waits for the
+ *              device and unbinds the map if it is the calling thread's bound one. 16 bytes of
+ *              device memory per texel (r, g, b and a pad: one tap is one aligned load). */
+#define BHRT_SKY_RGB32F 0
+#define BHRT_SKY_RGBA8  1
+typedef struct bhrt_sky bhrt_sky;   /* opaque; owned by the thread and device that made it */
+typedef struct { int32_t width, height, format, device; } bhrt_sky_state;
+
+/* A map of host_texels on the CURRENT device, complete on return. 0 and the handle in *sky, or -1
+ * with *sky untouched. */
+int  bhrt_sky_create(const void* host_texels, int width, int height, int format, bhrt_sky** sky);
+/* Waits for the device, unbinds the map if it is bound on this thread, frees it. NULL: no-op. */
+void bhrt_sky_destroy(bhrt_sky* sky);
+/* width, height, format, device. No HIP call. */
+int  bhrt_sky_info(const bhrt_sky* sky, bhrt_sky_state* state);
+/* The calling thread's map for frames with BHRT_FLAG_SKY; NULL unbinds. No HIP call. */
+int  bhrt_set_sky(const bhrt_sky* sky);
+/* The lookup alone: device_rgb[i] = the lookup of device_dirs[i], n >= 1 packed vectors, queued
+ * on hip_stream (NULL: ordered like the legacy default stream), no host wait. */
+int  bhrt_sky_lookup_device(const bhrt_sky* sky, const double* device_dirs /* [n][3] */, int n,
+                            double* device_rgb /* [n][3] */, void* hip_stream);
+/* The same on host arrays; waits. */
+int  bhrt_sky_lookup(const bhrt_sky* sky, const double* dirs, int n, double* rgb);
 
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);

@@ -12,6 +12,9 @@ RAY_HORIZON, RAY_DISK, RAY_BACKGROUND, RAY_MAX_DISTANCE, RAY_MAX_STEPS, RAY_ERRO
 INTEGRATOR_RK4, INTEGRATOR_RKF45, INTEGRATOR_LEAPFROG, INTEGRATOR_YOSHIDA = range(4)
 JITTER_NONE, JITTER_REGULAR_GRID, JITTER_RANDOM, JITTER_HALTON, JITTER_BLUE_NOISE = range(5)
 BHRT_FLAG_DOPPLER = 1
+BHRT_FLAG_SKY = 2      # non-disk, non-horizon colours from the thread's bound sky map
+BHRT_SKY_RGB32F = 0    # bhrt_sky_create formats: [H][W][3] float32
+BHRT_SKY_RGBA8 = 1     # [H][W][4] uint8, alpha ignored
 
 
 class Vector3D(C.Structure):
@@ -223,6 +226,12 @@ PARTICLE_DATA_SHAPES = {"positions": ((3,), np.float64), "velocities": ((3,), np
 class ParticleData(C.Structure):
     """bhrt_particle_data: device (or host) arrays of max_count elements, count [1]; any None."""
     _fields_ = [(f, C.c_void_p) for f in PARTICLE_DATA_FIELDS]
+
+
+class SkyState(C.Structure):
+    """bhrt_sky_state: a sky map's size, input format and device."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32),
+                ("device", C.c_int32)]
 
 
 class ParticlesState(C.Structure):

@@ -113,6 +113,13 @@ _PROTOS = {
     "bhrt_particles_kernel_ms": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
                                            _P(abi.SimulationConfig), C.c_int,
                                            _P(abi.ParticleData), _P(C.c_double * 5)]),
+    "bhrt_sky_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
+    "bhrt_sky_destroy": (None, [C.c_void_p]),
+    "bhrt_sky_info": (C.c_int, [C.c_void_p, _P(abi.SkyState)]),
+    "bhrt_set_sky": (C.c_int, [C.c_void_p]),
+    "bhrt_sky_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
+    "bhrt_sky_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -499,6 +506,55 @@ def particles_kernel_ms(ps, bh, cfg, max_count, out):
     _check(load().bhrt_particles_kernel_ms(ps, _ptr(bh), _ptr(cfg), int(max_count), _ptr(out),
                                            C.byref(ms)), "bhrt_particles_kernel_ms")
     return dict(zip(("update_plain", "update_counted", "scan", "scatter", "count_pass"), ms))
+
+
+def sky_create(texels):
+    """bhrt_sky_create on the current device from a numpy map: float32 [H, W, 3]
+    (BHRT_SKY_RGB32F) or uint8 [H, W, 4] (BHRT_SKY_RGBA8). The handle (an int) for the sky_*
+    calls and set_sky; free it with sky_destroy."""
+    t = np.ascontiguousarray(texels)
+    if t.dtype == np.uint8 and t.ndim == 3 and t.shape[2] == 4:
+        fmt = abi.BHRT_SKY_RGBA8
+    elif t.dtype == np.float32 and t.ndim == 3 and t.shape[2] == 3:
+        fmt = abi.BHRT_SKY_RGB32F
+    else:
+        raise BhrtError("sky_create: texels must be float32 [H, W, 3] or uint8 [H, W, 4]")
+    h = C.c_void_p()
+    _check(load().bhrt_sky_create(t.ctypes.data, t.shape[1], t.shape[0], fmt, C.byref(h)),
+           "bhrt_sky_create")
+    return h.value
+
+
+def sky_destroy(sky):
+    load().bhrt_sky_destroy(sky)
+
+
+def sky_state(sky):
+    """bhrt_sky_info as a dict (width, height, format, device)."""
+    s = abi.SkyState()
+    _check(load().bhrt_sky_info(sky, C.byref(s)), "bhrt_sky_info")
+    return {f: getattr(s, f) for f, _ in abi.SkyState._fields_}
+
+
+def set_sky(sky):
+    """bhrt_set_sky: the calling thread's map for frames with abi.BHRT_FLAG_SKY; None unbinds."""
+    _check(load().bhrt_set_sky(sky), "bhrt_set_sky")
+
+
+def sky_lookup_device(sky, dirs_ptr, n, rgb_ptr, stream=None):
+    """bhrt_sky_lookup_device: the lookup of n packed device vectors ([n][3] float64) into
+    [n][3] float64 device colours, asynchronous on a hipStream_t (int handle or None)."""
+    _check(load().bhrt_sky_lookup_device(sky, dirs_ptr, int(n), rgb_ptr,
+                                         C.c_void_p(stream) if stream else None),
+           "bhrt_sky_lookup_device")
+
+
+def sky_lookup(sky, dirs):
+    """bhrt_sky_lookup: the lookup of host vectors [n, 3]; returns float64 [n, 3]."""
+    d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    rgb = np.zeros_like(d)
+    _check(load().bhrt_sky_lookup(sky, d.ctypes.data, len(d), rgb.ctypes.data), "bhrt_sky_lookup")
+    return rgb
 
 
 def trace_paths_device(rays_ptr, n, bh, dk, cfg, method, max_positions, every, paths, hits,

@@ -188,7 +188,7 @@ static int ad_frame(devctx_t* c, hipStream_t st, const BlackHoleParams* bh,
     }
     /* the whole image's camera: rays are addressed by image pixel */
     bhrt_kparams kp;
-    bhrt_fill_scene(&kp, bh, dk, cfg, method, flags);
+    if (bhrt_fill_scene(&kp, bh, dk, cfg, method, flags)) return -1;
     bhrt_fill_camera(&kp, cam, W, H);
     bhrt_ad_rays_k rk;
     memset(&rk, 0, sizeof rk);
@@ -249,7 +249,7 @@ static int ad_frame(devctx_t* c, hipStream_t st, const BlackHoleParams* bh,
     memset(&xtr, 0, sizeof xtr);
     if (Nx > 0) {
         /* the second launch's own scratch first (what bhrt_rays_on_device asks for), then ours */
-        const size_t launch_bytes = align256((size_t)(BHRT_INIT_FIELDS + 1) * sizeof(double) * Nx);
+        const size_t launch_bytes = align256((size_t)BHRT_SCRATCH_FIELDS * sizeof(double) * Nx);
         char* q = (char*)bhrt_stream_scratch(c, st, launch_bytes + align256(24 * Nx) +
                                                         ad_planes_bytes(Nx, fused, 0));
         if (!q) return -1;

@@ -130,11 +130,11 @@ int bhrt_frame_on_device(const BlackHoleParams* bh, const AccretionDiskParams* d
     if (bhrt_colour_args_bad(out, (int)method, dk != NULL, bh->spin != 0.0)) return -1;
     if (!stream && bhrt_ctx_streams(c)) return -1;
     void* scratch = bhrt_stream_scratch(c, stream ? stream : c->stream,
-                                   (size_t)(BHRT_INIT_FIELDS + 1) * sizeof(double) *
+                                   (size_t)BHRT_SCRATCH_FIELDS * sizeof(double) *
                                        (size_t)nrows * (size_t)W);
     if (!scratch) return -1;
     bhrt_kparams kp;
-    bhrt_fill_scene(&kp, bh, dk, cfg, method, flags);
+    if (bhrt_fill_scene(&kp, bh, dk, cfg, method, flags)) return -1;
     bhrt_fill_camera(&kp, cam, W, H);
     if (rows && rows->num_shards > 1) {
         kp.cam.rows = *rows;
@@ -166,10 +166,10 @@ int bhrt_rays_on_device(const Ray* d_rays, const double* d_dirs, int n,
     if (!c) return -1;
     if (!stream && bhrt_ctx_streams(c)) return -1;
     void* scratch = bhrt_stream_scratch(c, stream ? stream : c->stream,
-                                   (size_t)(BHRT_INIT_FIELDS + 1) * sizeof(double) * (size_t)n);
+                                   (size_t)BHRT_SCRATCH_FIELDS * sizeof(double) * (size_t)n);
     if (!scratch) return -1;
     bhrt_kparams kp;
-    bhrt_fill_scene(&kp, bh, dk, cfg, method, flags);
+    if (bhrt_fill_scene(&kp, bh, dk, cfg, method, flags)) return -1;
     kp.src = BHRT_SRC_RAYS;
     kp.rays = d_rays;
     kp.init = (double*)scratch;
@@ -314,6 +314,8 @@ static int gather_frame(const BlackHoleParams* bh, const AccretionDiskParams* dk
                         IntegrationMethod method, int flags, const bhrt_frame_soa* out, int ndev,
                         int S, int total, int root, devctx_t* rc, hipStream_t rs) {
     const int B = 8;
+    for (int k = 0; k < (S == 1 ? 1 : ndev); k++) /* a sky map serves its own device only */
+        if (bhrt_sky_check(flags, (root + k) % total)) return -1;
     if (S == 1)
         return bhrt_frame_on_device(bh, dk, cfg, cam, W, H, NULL, method, flags, out, rs, 0);
     const bhrt_frame_soa fields = bhrt_device_fields(out, (int)method, dk != NULL, bh->spin != 0.0);

@@ -8,7 +8,7 @@
  *   host_frames.c  host-buffer frames in flight, readback, bhrt_trace_rays
  *   batch.c        trace_ray / trace_rays_batch: the pipelined chunks
  *   dropin.c       integrate_photon_path, trace_pixel, the bh_* context API
- *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c
+ *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c, sky.c
  *                  features with launchers of their own
  */
 #ifndef BHRT_HOST_H
@@ -185,6 +185,14 @@ int bhrt_fill_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const Accretion
                     const SimulationConfig* cfg, IntegrationMethod method, int flags);
 void bhrt_fill_camera(bhrt_kparams* kp, const bhrt_camera* cam, int W, int H);
 void bhrt_fill_origin(bhrt_kparams* kp, const Vector3D* origin);
+/* The thread's bound sky map (sky.c binds, bhrt_fill_scene copies it into a launch with
+ * BHRT_FLAG_SKY): bind k's record for `device` (NULL unbinds); the bound texels or NULL; and the
+ * refusal of a launch on `device` -- 0, or -1 with the error set where flags has BHRT_FLAG_SKY and
+ * no map is bound or the bound one lives on another device. No HIP call. bhrt_fill_scene makes
+ * that check for the current device and returns -1 the same way. */
+void bhrt_sky_bind(const bhrt_sky_k* k, int device);
+const void* bhrt_sky_bound(void);
+int bhrt_sky_check(int flags, int device);
 /* whether the trace kernel writes this scene's colour outputs */
 int bhrt_colour_fused(int method, int has_disk, int spin);
 int bhrt_colour_args_bad(const bhrt_frame_soa* out, int method, int has_disk, int spin);

@@ -25,6 +25,9 @@ enum { BHRT_INIT_FIELDS = 21 }; /* ray arrays: y0..y5, y6, y7, dx, dy, dz, px, p
                                    far_ok, sin/cos of y1, y2, y3; camera frames use the first
                                    BHRT_INIT_FIELDS_CAMERA rows (the rest is the shared origin) */
 enum { BHRT_INIT_FIELDS_CAMERA = 8 }; /* y4, y5, y6, y7, dx, dy, dz, far_ok */
+enum { BHRT_SCRATCH_FIELDS = BHRT_INIT_FIELDS + 1 + 3 }; /* a launch's scratch, in doubles per ray:
+                                   the init table, the redo list, and the exit chords a sky frame
+                                   hands to the separate colour pass (bhrt_sky_k.chord) */
 
 typedef struct {
     /* scene constants (raytracer.c:65-130, 465, 556-571, 652-659; spacetime.c:22) */
@@ -78,6 +81,18 @@ typedef struct {
     int ntiles, tile_stride;         /* tile_stride > 0: the claim order visits tile
                                         (t * tile_stride) mod ntiles at step t (scatter) */
 } bhrt_camera_k;
+
+/* The bound sky map of a launch with BHRT_FLAG_SKY (the rule: include/bhrt_api.h "Sky maps"); all
+ * zero otherwise. The record is the calling thread's (scene.c bhrt_sky_bind), copied here by
+ * bhrt_fill_scene; the kernels read it at a ray's exit only (geodesic.hip sky_lookup). */
+typedef struct {
+    const void* tex;      /* device [h][w] texels, 16 bytes each: r, g, b as float and a pad, so
+                             one tap is one aligned load; NULL: no sky */
+    int w, h;
+    double sx, sy;        /* RN(w / (2 pi)), RN(h / pi): texels per radian */
+    double* chord;        /* the separate colour pass only (colour_fused == 0): [3][n] scratch,
+                             the exit chord of every RAY_MAX_DISTANCE ray (set per launch) */
+} bhrt_sky_k;
 
 /* Whether the trace kernel writes a scene's colour outputs at each ray's exit, from the state in
  * registers (no separate colour pass re-reading the hits). Every scene does: the separate pass
@@ -133,6 +148,8 @@ typedef struct {
                              than this take half the grid (0 = off) */
     int diag_slot;        /* the launch's control-block slot (the BHRT_WAVE_STAMPS diagnostic
                              build records per-wave stamps under it; unused otherwise) */
+    bhrt_sky_k sky;       /* sc.flags & BHRT_FLAG_SKY: the sky map. Last, so that every other
+                             field keeps its place in the kernel argument segment */
 } bhrt_kparams;
 
 /* Supersampled camera frames (supersample.c; geodesic.hip k_ss_rays, k_ss_resolve): two
@@ -294,6 +311,11 @@ int bhrt_launch_particles_scan(const int* d_block_active, int nblocks, int* d_of
 int bhrt_launch_particles_scatter(const Particle* d_particles, int count, const int* d_offsets,
                                   int max_count, const bhrt_particle_data* out, void* stream,
                                   void* ev0, void* ev1);
+
+/* Sky lookups by themselves (sky.c; geodesic.hip k_sky_lookup): rgb[i] = the lookup of dirs[i],
+ * n > 0 directions, asynchronous on `stream`; 0 or a hipError_t value */
+int bhrt_launch_sky(const bhrt_sky_k* sky, const double* d_dirs, int n, double* d_rgb,
+                    void* stream);
 
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel

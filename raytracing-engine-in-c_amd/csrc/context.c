@@ -415,6 +415,13 @@ int bhrt_ctx_launch_fn(devctx_t* c, bhrt_kparams* kp, hipStream_t stream, bhrt_l
     }
     /* the redo list follows the initial-state table (one extra field of the allocation) */
     if (kp->init) kp->redo = (int*)(kp->init + (size_t)BHRT_INIT_FIELDS * (size_t)kp->n);
+    /* a sky frame's separate colour pass reads the exit chords from the three fields behind it */
+    if (kp->sky.tex && !fn) {
+        if (bhrt_sky_check(kp->sc.flags, c->device)) return -1;
+        kp->sky.chord = kp->init && !kp->colour_fused
+                            ? kp->init + (size_t)(BHRT_INIT_FIELDS + 1) * (size_t)kp->n
+                            : NULL;
+    }
     if (c->npend == BHRT_RING && harvest(c, 1, stream, BHRT_RING / 2) != 0) return -1;
     if (ring_order(c, stream)) return -1;
     int slot = c->next_slot;

@@ -1206,6 +1206,25 @@ __device__ __forceinline__ bool disk_hit(const Ray_& R, double nx, double ny, do
 
 enum Term : int { T_NONE = 0, T_HORIZON, T_DISK, T_MAXDIST, T_MAXSTEPS };
 
+// p_{k-1}, the point a ray's last iteration started from, for the sky lookup at its exit: the
+// exit chord is p_k - p_{k-1}, taken there (exit_chord). Only the point is kept in the loop -- a
+// copy, no arithmetic -- so that the sky instantiations' iterations are the plain ones' operation
+// for operation (a difference formed in the loop would give the compiler other products to
+// contract, and a disk hit other bits). Kept beside Ray_, by k_trace's sky instantiations alone: as
+// a part of Ray_ it would grow the stack objects of the kernels that hold the ray in memory (the
+// redo pass, k_path) whether they have a sky or not.
+struct Chord {
+    double x, y, z;
+};
+// RN(p_k - p_{k-1}) per component, no contraction: what the rule's reader forms from two path points
+__device__ __forceinline__ void exit_chord(const Chord& prev, double px, double py, double pz,
+                                           double& cx, double& cy, double& cz) {
+#pragma clang fp contract(off)
+    cx = px - prev.x;
+    cy = py - prev.y;
+    cz = pz - prev.z;
+}
+
 struct HSel {  // the four step sizes of the schedule, hoisted out of the kernel argument block
     double far_, r15, r5, r2_5;
     double big;  // 2^100, the disk test's bound on |den| (disk_hit): an SGPR pair set once,
@@ -1287,10 +1306,14 @@ constexpr bool h6cache() {
 // hit is noted in the sign bit of R.k, where the step-budget compare (unsigned) sees it; the
 // caller forms the termination on the trip's exit edge (exit_term). The iteration itself is the
 // same arithmetic either way.
+// SKY (k_trace's sky instantiations): the point the iteration started from, p_{k-1}, is kept in
+// *ch (Chord). A lane runs no iteration after the one that ends its ray
+// (the wave-uniform trips leave on the iteration in which any lane stops, the predicated ones
+// skip a lane that stopped), so at the exit it is the terminating iteration's.
 template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, bool ACC = false,
-          bool MASK = false>
+          bool MASK = false, bool SKY = false>
 __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray_iterate(
-    Ray_& R, const Scene& sc, Counters& n, const HSel hs) {
+    Ray_& R, const Scene& sc, Counters& n, const HSel hs, Chord* ch = nullptr) {
     static_assert(!MASK || (DISK && METHOD == INTEGRATOR_RK4), "MASK: every iteration moves");
     Counters* const hc = HUGE ? nullptr : &n;
     // Instantiations with repair_at_refill() run the recovery once, when the ray is loaded:
@@ -1398,6 +1421,11 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
     sph2cart_t(R.y[1], R.s2, R.c2, R.s3, R.c3, x, y, z);
     const double ox = R.px, oy = R.py, oz = R.pz;
     R.dist += seg_len(x - ox, y - oy, z - oz);
+    if constexpr (SKY) {
+        ch->x = ox;
+        ch->y = oy;
+        ch->z = oz;
+    }
     R.px = x;
     R.py = y;
     R.pz = z;
@@ -1655,6 +1683,78 @@ __device__ __forceinline__ void colour_of(const Scene& sc, int res, double hx, d
     }
 }
 
+// Sky maps (the rule: include/bhrt_api.h "Sky maps"; tests/sky_rule.py restates it): the
+// bilinear lookup of direction d in the launch's equirectangular map. IEEE double, no
+// contraction, so the trace kernel's exit, the separate colour pass and k_sky_lookup give the same
+// bits. Every index is wrapped (columns) or clamped (rows) after it is formed, so no operand --
+// not even a NaN -- reads outside the map's w * h texels.
+__device__ __forceinline__ void sky_lookup(const bhrt_sky_k& sk, double dx, double dy, double dz,
+                                           double& r, double& g, double& b) {
+#pragma clang fp contract(off)
+    const double L = sqrt((dx * dx + dy * dy) + dz * dz);
+    if (!(L > 0.0 && L <= 1.79769313486231570815e+308)) {  // zero, overflowed or NaN: black
+        r = g = b = 0.0;
+        return;
+    }
+    const double th = acos(clampd(dz / L, -1.0, 1.0));
+    const double ph = atan2(dy, dx);
+    const double fx = (ph + 3.14159265358979323846) * sk.sx - 0.5;
+    const double fy = th * sk.sy - 0.5;
+    const double fi = floor(fx), fj = floor(fy);
+    const double wx = fx - fi, wy = fy - fj;
+    const int w = sk.w, h = sk.h;
+    int i0 = (int)fi % w, i1 = ((int)fi + 1) % w;
+    i0 += i0 < 0 ? w : 0;
+    i1 += i1 < 0 ? w : 0;
+    const int j0 = min(max((int)fj, 0), h - 1), j1 = min(max((int)fj + 1, 0), h - 1);
+    const float4* const T = static_cast<const float4*>(sk.tex);
+    const float4 t00 = T[(size_t)j0 * w + i0], t01 = T[(size_t)j0 * w + i1];
+    const float4 t10 = T[(size_t)j1 * w + i0], t11 = T[(size_t)j1 * w + i1];
+    const double ux = 1.0 - wx, uy = 1.0 - wy;
+    r = ((double)t00.x * ux + (double)t01.x * wx) * uy + ((double)t10.x * ux + (double)t11.x * wx) * wy;
+    g = ((double)t00.y * ux + (double)t01.y * wx) * uy + ((double)t10.y * ux + (double)t11.y * wx) * wy;
+    b = ((double)t00.z * ux + (double)t01.z * wx) * uy + ((double)t10.z * ux + (double)t11.z * wx) * wy;
+}
+
+// The colour of one ray of a sky launch: disk and horizon as colour_of; a RAY_MAX_DISTANCE ray
+// looks up its exit chord c (a chord with a non-finite component, or whose squared length is not
+// > 0, does not count); every other ray the direction the gradient reads, d. `res` is the ray's
+// full class. One function for the trace kernel's exit and the separate pass.
+// NOT inlined, the one call of the sky instantiations (at a ray's exit, outside the iterations):
+// inlined into k_trace, the lookup's acos / atan2 changed how the compiler compiled the ITERATIONS
+// around it -- on the few rays per frame that take a rare path (a wide trig shift, the literal
+// accelerations) it folded the other product of an a*b + c*d into the FMA -- and a disk pixel of
+// a sky frame was not the flagless frame's bit for bit (C2 at max distance 20, 48x27: 5 of 774
+// disk pixels, 1.7e-14 relative). Behind a call the iterations compile as the plain
+// instantiation's, and the disk and horizon pixels are its bits (test_gpu_sky.py).
+template <bool DISK>
+__device__ __attribute__((noinline)) void colour_of_sky(const Scene& sc, const bhrt_sky_k& sk, int res,
+                                              double hx, double hy, double dx, double dy,
+                                              double dz, double cx, double cy, double cz,
+                                              double& r, double& g, double& b) {
+#pragma clang fp contract(off)
+    if (res == RAY_DISK || res == RAY_HORIZON) {
+        if constexpr (DISK)
+            colour_of(sc, res, hx, hy, dx, dy, dz, r, g, b);
+        else
+            colour_sky(res, dy, r, g, b);
+        return;
+    }
+    double vx = dx, vy = dy, vz = dz;
+    if (res == RAY_MAX_DISTANCE) {
+        const double l2 = (cx * cx + cy * cy) + cz * cz;
+        const bool fin = fabs(cx) <= 1.79769313486231570815e+308 &&
+                         fabs(cy) <= 1.79769313486231570815e+308 &&
+                         fabs(cz) <= 1.79769313486231570815e+308;
+        if (fin && l2 > 0.0) {
+            vx = cx;
+            vy = cy;
+            vz = cz;
+        }
+    }
+    sky_lookup(sk, vx, vy, vz, r, g, b);
+}
+
 __device__ __forceinline__ void store_colour(const bhrt_frame_soa& s, int i, double r, double g,
                                              double b) {
     if (s.rgb_r) {
@@ -1685,9 +1785,36 @@ __device__ __forceinline__ const bhrt_kparams& cold(const bhrt_kparams&) {
     return *(const bhrt_kparams*)p;
 }
 
-template <bool DISK>
-__device__ __forceinline__ void store_ray(const bhrt_kparams& kp, int i, const Ray_& R, int term) {
+// SKY (a launch with a sky map; kp is cold(kp), so the map's fields are loaded here, at the exit,
+// and hold no registers across the loop): the colour through colour_of_sky, or -- separate colour
+// pass -- a RAY_MAX_DISTANCE ray's chord into the launch scratch for k_colour.
+template <bool DISK, bool SKY = false>
+__device__ __forceinline__ void store_ray(const bhrt_kparams& kp, int i, const Ray_& R, int term,
+                                          const Chord& ch) {
     store_hit(kp.out, i, R, term, kp.sc);
+    if constexpr (SKY) {
+        if (!(kp.out.rgb_r || kp.out.rgba32f || kp.out.rgba8)) return;
+        if (!kp.colour_fused) {
+            if (term == T_MAXDIST && kp.sky.chord) {
+                const size_t n = (size_t)kp.n;
+                double cx, cy, cz;
+                exit_chord(ch, R.px, R.py, R.pz, cx, cy, cz);
+                kp.sky.chord[i] = cx;
+                kp.sky.chord[n + i] = cy;
+                kp.sky.chord[2 * n + i] = cz;
+            }
+            return;
+        }
+        const int res = term == T_DISK      ? RAY_DISK
+                        : term == T_HORIZON ? RAY_HORIZON
+                        : term == T_MAXDIST ? RAY_MAX_DISTANCE
+                                            : RAY_MAX_STEPS;
+        double r, g, b, cx, cy, cz;
+        exit_chord(ch, R.px, R.py, R.pz, cx, cy, cz);  // (read for RAY_MAX_DISTANCE alone)
+        colour_of_sky<DISK>(kp.sc, kp.sky, res, R.px, R.py, R.dx, R.dy, R.dz, cx, cy, cz, r, g, b);
+        store_colour(kp.out, i, r, g, b);
+        return;
+    }
     if (kp.colour_fused && (kp.out.rgb_r || kp.out.rgba32f || kp.out.rgba8)) {
         const int res = term == T_DISK ? RAY_DISK : (term == T_HORIZON ? RAY_HORIZON : RAY_MAX_STEPS);
         double r, g, b;
@@ -1930,7 +2057,11 @@ constexpr int unroll_n() {
 // a = 0 RK4 disk path; ray arrays from trace_rays_batch take 2, so a chunk's
 // trace depends on its upload alone (no set-up kernel queued behind the previous chunk's).
 // The sin/cos anchors of the shared origin are the same for every ray: computed once per wave.
-template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, int INL = 0, bool ACC = false>
+// SKY: the launch has a sky map (kp.sky): the iterations keep their chord (ray_iterate) and the
+// exit looks the map up (store_ray). Instantiated for sky launches only; every other
+// instantiation is the code it was.
+template <int METHOD, bool DISK, bool SPIN0, bool FAR, bool HUGE, int INL = 0, bool ACC = false,
+          bool SKY = false>
 __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     const unsigned long long total =
         HUGE ? *(volatile unsigned long long*)(kp.ctl + 6) : (unsigned long long)kp.n;
@@ -1954,6 +2085,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     const unsigned long long below = (1ull << lane) - 1ull;
     Counters n;
     Ray_ R;
+    Chord ch{0.0, 0.0, 0.0};  // (read by the sky instantiations only)
     int rid = 0;
     bool live = false;
     // Ray queues. The rays are dealt, in blocks of 64 consecutive ids, round
@@ -2003,7 +2135,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
             st_refills++;
 #endif
             if constexpr (DEFER) {
-                if (pterm != T_NONE) store_ray<DISK>(kc, rid, R, pterm);
+                if (pterm != T_NONE) store_ray<DISK, SKY>(kc, rid, R, pterm, ch);
                 pterm = T_NONE;
             }
             bool ok;
@@ -2140,7 +2272,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                     n.rays++;
                     live = true;
                     if (kp.sc.max_steps <= 0) {  // loop never runs: MAX_STEPS, steps 0
-                        store_ray<DISK>(kc, rid, R, T_MAXSTEPS);
+                        store_ray<DISK, SKY>(kc, rid, R, T_MAXSTEPS, ch);
                         live = false;
                         n.clear_huge();
                     }
@@ -2151,7 +2283,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
         if (n_live == 0) {
             if (exhausted) {
                 if constexpr (DEFER) {
-                    if (pterm != T_NONE) store_ray<DISK>(kc, rid, R, pterm);
+                    if (pterm != T_NONE) store_ray<DISK, SKY>(kc, rid, R, pterm, ch);
                 }
                 break;
             }
@@ -2168,16 +2300,16 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
             if constexpr (exit_masks<METHOD, DISK, SPIN0>()) {
                 // (the wave-uniform guard below, on the wave's exit mask)
                 unsigned long long stop =
-                    ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true>(R, kp.sc, n, hsel);
+                    ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true, SKY>(R, kp.sc, n, hsel, &ch);
 #pragma unroll
                 for (int u = 1; u < unroll_n<METHOD, SPIN0, FAR, HUGE, ACC>(); u++) {
                     if (stop != 0ull) break;  // (a lane that raised `huge` is marked: Counters)
-                    stop = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true>(R, kp.sc, n, hsel);
+                    stop = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, true, SKY>(R, kp.sc, n, hsel, &ch);
                 }
                 term = T_NONE;
                 if (stop != 0ull) term = exit_term(R, kp.sc);
             } else if constexpr (uniform_trip<METHOD, SPIN0>()) {
-                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
+                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, false, SKY>(R, kp.sc, n, hsel, &ch);
                 // wave-uniform guard: the trip goes on only while EVERY live lane does, so the
                 // next iteration runs on the same exec mask -- no per-lane region around it, and
                 // no copies of the values a lane that stopped must keep (they are copied once, on
@@ -2185,14 +2317,14 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
 #pragma unroll
                 for (int u = 1; u < unroll_n<METHOD, SPIN0, FAR, HUGE, ACC>(); u++) {
                     if (__ballot(term != T_NONE || n.huge) != 0ull) break;
-                    term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
+                    term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, false, SKY>(R, kp.sc, n, hsel, &ch);
                 }
             } else {
-                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
+                term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, false, SKY>(R, kp.sc, n, hsel, &ch);
 #pragma unroll
                 for (int u = 1; u < unroll_n<METHOD, SPIN0, FAR, HUGE, ACC>(); u++)
                     if (term == T_NONE && !n.huge)
-                        term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC>(R, kp.sc, n, hsel);
+                        term = ray_iterate<METHOD, DISK, SPIN0, FAR, HUGE, ACC, false, SKY>(R, kp.sc, n, hsel, &ch);
             }
             if (METHOD == INTEGRATOR_RK4 && (term != T_NONE || (!HUGE && n.huge)))
                 n.iters += R.k;  // every RK4 iteration moves, so R.k = iterations executed
@@ -2209,7 +2341,7 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
                 if constexpr (DEFER)
                     pterm = term;
                 else
-                    store_ray<DISK>(kc, rid, R, term);
+                    store_ray<DISK, SKY>(kc, rid, R, term, ch);
                 live = false;
             }
         }
@@ -2254,7 +2386,8 @@ __global__ BHRT_TRACE_BOUNDS void k_trace(const bhrt_kparams kp) {
     }
 }
 
-template <int SRC>
+// SKY: a sky launch's pass (its own instantiation: the plain pass keeps its registers)
+template <int SRC, bool SKY = false>
 __global__ __launch_bounds__(256) void k_colour(const bhrt_kparams kp) {
     const bhrt_frame_soa& s = kp.out;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kp.n; i += gridDim.x * blockDim.x) {
@@ -2273,12 +2406,32 @@ __global__ __launch_bounds__(256) void k_colour(const bhrt_kparams kp) {
         }
         const int res = s.result[i];
         double r, g, b;
-        colour_of(kp.sc, res, res == RAY_DISK ? s.hit_x[i] : 0.0,
-                  res == RAY_DISK ? s.hit_y[i] : 0.0, dx, dy, dz, r, g, b);
+        const double hx = res == RAY_DISK ? s.hit_x[i] : 0.0, hy = res == RAY_DISK ? s.hit_y[i] : 0.0;
+        if constexpr (SKY) {  // the chords of the launch's RAY_MAX_DISTANCE rays are in the scratch
+            const size_t n = (size_t)kp.n;
+            const bool md = res == RAY_MAX_DISTANCE && kp.sky.chord;
+            colour_of_sky<true>(kp.sc, kp.sky, res, hx, hy, dx, dy, dz, md ? kp.sky.chord[i] : 0.0,
+                                md ? kp.sky.chord[n + i] : 0.0, md ? kp.sky.chord[2 * n + i] : 0.0,
+                                r, g, b);
+        } else {
+            colour_of(kp.sc, res, hx, hy, dx, dy, dz, r, g, b);
+        }
         store_colour(s, i, r, g, b);
     }
     __syncthreads();  // the frame is complete once the last workgroup's stores are (ctl[10])
     if (threadIdx.x == 0) atomicMax(kp.ctl + 10, (unsigned long long)wall_clock64());
+}
+
+// bhrt_sky_lookup_device: sky_lookup of n packed directions, one lane each
+__global__ __launch_bounds__(256) void k_sky_lookup(const bhrt_sky_k sk, const double* dirs, int n,
+                                                    double* rgb) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double r, g, b;
+    sky_lookup(sk, dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], r, g, b);
+    rgb[3 * i] = r;
+    rgb[3 * i + 1] = g;
+    rgb[3 * i + 2] = b;
 }
 
 // Supersampled frames (bhrt_kernel.h bhrt_ss_rays_k): the directions of one sample's rays, one
@@ -2902,8 +3055,8 @@ int claim_shift(int blocks, int claim_div, int queue_bits, int lanes = 256) {
     return shift;
 }
 
-template <int METHOD, bool DISK, bool SPIN0, bool FAR, int INL, bool ACC = false>
-void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
+template <int METHOD, bool DISK, bool SPIN0, bool FAR, int INL, bool ACC, bool SKY>
+void launch_trace_pair_t(const bhrt_kparams& kp, hipStream_t st) {
     // resident workgroups of the two instantiations, per device (and per hot block size:
     // kp.block_lanes, 64/128/256 lanes -- a workgroup's slot frees only once ALL its waves
     // have drained, so small launches prefer one wave per workgroup)
@@ -2915,10 +3068,10 @@ void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
     int cap_huge = grid_huge[dev].load(std::memory_order_relaxed);
     if (cap == 0 || cap_huge == 0) {
         cap = resident_blocks(
-            reinterpret_cast<const void*>(&k_trace<METHOD, DISK, SPIN0, FAR, false, INL, ACC>), dev,
+            reinterpret_cast<const void*>(&k_trace<METHOD, DISK, SPIN0, FAR, false, INL, ACC, SKY>), dev,
             lanes);
         cap_huge = resident_blocks(
-            reinterpret_cast<const void*>(&k_trace<METHOD, DISK, SPIN0, FAR, true, INL>), dev);
+            reinterpret_cast<const void*>(&k_trace<METHOD, DISK, SPIN0, FAR, true, INL, false, SKY>), dev);
         grid_cap[dev][bi].store(cap, std::memory_order_relaxed);
         grid_huge[dev].store(cap_huge, std::memory_order_relaxed);
     }
@@ -2949,7 +3102,7 @@ void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
     if (blocks < 1) blocks = 1;
     bhrt_kparams k = kp;
     k.claim_shift = claim_shift(blocks, kp.claim_div, kp.queue_bits, lanes);
-    k_trace<METHOD, DISK, SPIN0, FAR, false, INL, ACC><<<blocks, lanes, 0, st>>>(k);
+    k_trace<METHOD, DISK, SPIN0, FAR, false, INL, ACC, SKY><<<blocks, lanes, 0, st>>>(k);
     // A launch the host proved eviction-free (scene.c origin_no_evict: every ray starts at
     // one origin, and every state the loop can reach keeps its sincos arguments below 2^20 --
     // C1, C2, C3 -- or, on the zero-acceleration paths, C4 and C5, the loop has no sincos and
@@ -2964,7 +3117,17 @@ void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
     int redo_blocks = (FAR && !kp.sc.far_bounded) ? blocks : (blocks < 64 ? blocks : 64);
     if (redo_blocks > cap_huge) redo_blocks = cap_huge;
     k.claim_shift = claim_shift(redo_blocks, kp.claim_div, 0);  // (the redo list is one queue)
-    k_trace<METHOD, DISK, SPIN0, FAR, true, INL><<<redo_blocks, 256, 0, st>>>(k);
+    k_trace<METHOD, DISK, SPIN0, FAR, true, INL, false, SKY><<<redo_blocks, 256, 0, st>>>(k);
+}
+
+// the pair of a launch: its sky instantiations where it has a sky map (bhrt_fill_scene sets
+// kp.sky only with BHRT_FLAG_SKY), else the plain ones
+template <int METHOD, bool DISK, bool SPIN0, bool FAR, int INL, bool ACC = false>
+void launch_trace_pair(const bhrt_kparams& kp, hipStream_t st) {
+    if (kp.sky.tex)
+        launch_trace_pair_t<METHOD, DISK, SPIN0, FAR, INL, ACC, true>(kp, st);
+    else
+        launch_trace_pair_t<METHOD, DISK, SPIN0, FAR, INL, ACC, false>(kp, st);
 }
 
 template <int METHOD, bool DISK, bool SPIN0, bool FAR>
@@ -3021,7 +3184,15 @@ int launch_t(const bhrt_kparams& kp, hipStream_t st, hipEvent_t ev0, hipEvent_t 
     }
     if (ev1) (void)hipEventRecord(ev1, st);
     if (!kp.colour_fused && (kp.out.rgb_r || kp.out.rgba32f || kp.out.rgba8)) {
-        if (kp.src == BHRT_SRC_CAMERA)
+        if (kp.sky.tex && kp.src == BHRT_SRC_CAMERA)
+            k_colour<BHRT_SRC_CAMERA, true><<<grid_for(reinterpret_cast<const void*>(
+                                                           &k_colour<BHRT_SRC_CAMERA, true>),
+                                                       kp.n), 256, 0, st>>>(kp);
+        else if (kp.sky.tex)
+            k_colour<BHRT_SRC_RAYS, true><<<grid_for(reinterpret_cast<const void*>(
+                                                         &k_colour<BHRT_SRC_RAYS, true>),
+                                                     kp.n), 256, 0, st>>>(kp);
+        else if (kp.src == BHRT_SRC_CAMERA)
             k_colour<BHRT_SRC_CAMERA><<<grid_for(reinterpret_cast<const void*>(&k_colour<BHRT_SRC_CAMERA>),
                                                  kp.n), 256, 0, st>>>(kp);
         else
@@ -3100,6 +3271,14 @@ extern "C" int bhrt_launch_paths(const bhrt_kparams* kp, const bhrt_paths_k* pk,
     case INTEGRATOR_RKF45: return launch_paths_m<INTEGRATOR_RKF45>(*kp, *pk, st, e0, e1);
     default: return launch_paths_m<INTEGRATOR_LEAPFROG>(*kp, *pk, st, e0, e1);  // no-op integrators
     }
+}
+
+extern "C" int bhrt_launch_sky(const bhrt_sky_k* sky, const double* d_dirs, int n, double* d_rgb,
+                               void* stream) {
+    if (n <= 0) return 0;
+    k_sky_lookup<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream)>>>(*sky, d_dirs, n,
+                                                                               d_rgb);
+    return (int)hipGetLastError();
 }
 
 extern "C" int bhrt_launch_trace(const bhrt_kparams* kp, void* stream, void* ev0, void* ev1) {

@@ -417,6 +417,8 @@ static int render_frame_issue(const BlackHoleParams* bh, const AccretionDiskPara
     f->H = H;
     f->host = *host;
     f->timing = getenv("BHRT_HOST_TIMING") != NULL;
+    for (int d = 0; d < ndev; d++) /* a sky map serves its own device only: before any launch */
+        if (bhrt_sky_check(flags, d)) return -1;
     if (frame_enqueue(f, bh, dk, cfg, cam, method, flags)) {
         frame_abort(f, ndev);
         return -1;
@@ -455,6 +457,8 @@ int bhrt_trace_rays(const Ray* rays, int n, const BlackHoleParams* bh,
         return -1;
     }
     if (n < 4096 * ndev) ndev = 1; /* small batches: one device, one launch */
+    for (int d = 0; d < ndev; d++) /* a sky map serves its own device only: before any launch */
+        if (bhrt_sky_check(flags, d)) return -1;
     shard_job jobs[BHRT_MAX_DEV];
     long base[BHRT_MAX_DEV + 1];
     for (int d = 0; d <= ndev; d++) base[d] = (long)n * d / ndev;

@@ -180,9 +180,41 @@ static int origin_no_evict(const bhrt_scene_k* s, double r, double th, double ph
     return isfinite(B) && B * sl < 1048576.0;
 }
 
+/* The calling thread's bound sky map (bhrt_set_sky, sky.c): the record a launch with
+ * BHRT_FLAG_SKY copies into its parameters, and the device that holds the texels. Kept here, in
+ * the host core, so that no core file names a sky launcher. */
+static __thread bhrt_sky_k g_sky;
+static __thread int g_sky_dev = -1;
+
+void bhrt_sky_bind(const bhrt_sky_k* k, int device) {
+    if (k) g_sky = *k;
+    else memset(&g_sky, 0, sizeof g_sky);
+    g_sky_dev = k ? device : -1;
+}
+
+const void* bhrt_sky_bound(void) { return g_sky.tex; }
+
+int bhrt_sky_check(int flags, int device) {
+    if (!(flags & BHRT_FLAG_SKY)) return 0;
+    if (!g_sky.tex) {
+        set_err("BHRT_FLAG_SKY: no sky map is bound on this thread (bhrt_set_sky)");
+        return -1;
+    }
+    if (device != g_sky_dev) {
+        set_err("BHRT_FLAG_SKY: the bound sky map lives on device %d, the launch is for device %d",
+                g_sky_dev, device);
+        return -1;
+    }
+    return 0;
+}
+
 int bhrt_fill_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const AccretionDiskParams* dk,
                     const SimulationConfig* cfg, IntegrationMethod method, int flags) {
     memset(kp, 0, sizeof *kp);
+    if (flags & BHRT_FLAG_SKY) { /* before any launch of the call: the launch's device is current */
+        if (bhrt_sky_check(flags, bhrt_current_device())) return -1;
+        kp->sky = g_sky;
+    }
     bhrt_scene_k* s = &kp->sc;
     const double rs = bh->schwarzschild_radius, dt = cfg->time_step;
     /* the products the reference forms inline (raytracer.c:65-130, 465, 556-571, 652) */

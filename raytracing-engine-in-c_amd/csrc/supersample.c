@@ -115,7 +115,7 @@ static int ss_frame(devctx_t* c, hipStream_t st, const BlackHoleParams* bh,
     const size_t N = (size_t)n * (size_t)k->samples;
     const int fused = bhrt_colour_fused((int)method, dk != NULL, bh->spin != 0.0);
     /* the trace launch's own scratch first (what bhrt_rays_on_device asks for), then ours */
-    const size_t launch_bytes = align256((size_t)(BHRT_INIT_FIELDS + 1) * sizeof(double) * N);
+    const size_t launch_bytes = align256((size_t)BHRT_SCRATCH_FIELDS * sizeof(double) * N);
     const size_t plane8 = align256(8 * N), plane4 = align256(4 * N);
     const size_t bytes = launch_bytes + align256(24 * N) + 3 * plane8 + plane4 +
                          (fused ? 0 : 2 * plane8);
@@ -137,7 +137,7 @@ static int ss_frame(devctx_t* c, hipStream_t st, const BlackHoleParams* bh,
         smp.hit_y = (double*)(p + plane8);
     }
     bhrt_kparams kp;
-    bhrt_fill_scene(&kp, bh, dk, cfg, method, flags);
+    if (bhrt_fill_scene(&kp, bh, dk, cfg, method, flags)) return -1;
     bhrt_fill_camera(&kp, cam, W, H);
     if (rows && rows->num_shards > 1) { /* (as bhrt_frame_on_device sets a shard up) */
         kp.cam.rows = *rows;
