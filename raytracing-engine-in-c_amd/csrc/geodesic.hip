@@ -950,9 +950,18 @@ __device__ __forceinline__ double len3(double x, double y, double z) {
     return sqrt((x * x + y * y) + z * z);  // vector3D_length (math_util.c:85-113)
 }
 // the per-iteration path length |p - p_prev| of the hot loop: it only feeds the running
-// distance (a sum of up to max_steps of them, compared with max_dist)
+// distance (a sum of up to max_steps of them, compared with max_dist).
+// sqrt_nr1(+Inf) is NaN (rsq gives 0, and Inf * 0), where vector3D_length's sqrt is +Inf and the
+// ray ends as MAX_DISTANCE: a segment from an infinite origin, or one whose squares overflow
+// (longer than 1.3e154). WIDE (the general instantiation: k_path, k_paths, the HUGE redo) keeps
+// the reference's value there; the hot instantiations never see such a segment behind a finite
+// origin (their state is bounded, repair_at_refill).
+template <bool WIDE>
 __device__ __forceinline__ double seg_len(double x, double y, double z) {
-    return sqrt_nr1((x * x + y * y) + z * z);
+    const double q = (x * x + y * y) + z * z;
+    const double s = sqrt_nr1(q);
+    if (WIDE) return q == __builtin_inf() ? q : s;
+    return s;
 }
 
 struct Ray_ {
@@ -1420,7 +1429,7 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
     }
     sph2cart_t(R.y[1], R.s2, R.c2, R.s3, R.c3, x, y, z);
     const double ox = R.px, oy = R.py, oz = R.pz;
-    R.dist += seg_len(x - ox, y - oy, z - oz);
+    R.dist += seg_len<HUGE>(x - ox, y - oy, z - oz);
     if constexpr (SKY) {
         ch->x = ox;
         ch->y = oy;
