@@ -863,6 +863,112 @@ int  bhrt_sky_lookup_device(const bhrt_sky* sky, const double* device_dirs /* [n
 /* The same on host arrays; waits. */
 int  bhrt_sky_lookup(const bhrt_sky* sky, const double* dirs, int n, double* rgb);
 
+/* ---- Physical geodesics: a Kerr-Schild null-ray tracer beside the parity path ----
+ * The calls above reproduce the reference ray for ray: with spin != 0 its accelerations are zero
+ * ("Kerr geodesic equations would go here", raytracer.c:131-138) and every ray is a straight line;
+ * with spin == 0 the state is read index-shifted and clamped. The bhrt_kerr_* calls trace true null
+ * geodesics of Kerr (Schwarzschild is spin 0) instead: an opt-in path with its own kernel, which
+ * changes nothing in the calls above.
+ *
+ * THE RULE (tests/kerr_rule.py restates it in numpy). All arithmetic is IEEE double.
+ *  Time reversal. The ray of image direction n is the time reverse of the photon that arrives from
+ *              n, and time reversal maps Kerr(a) onto Kerr(-a): the kernel integrates a
+ *              future-directed photon that leaves the origin along n, in ingoing Kerr-Schild
+ *              coordinates of spin a~ = -(spin * mass). Rays cross the future horizon smoothly; for
+ *              spin > 0 about +z the flat prograde edge of the shadow lies on the side of the image
+ *              where the hole turns toward the observer. All positions -- origins, hit points,
+ *              chords, the disk -- are Kerr-Schild Cartesian coordinates: at spin 0 the project's
+ *              spherical identification, far from the hole flat space.
+ *  Geometry    at (x, y, z): rho^2 = x^2 + y^2 + z^2, w = rho^2 - a~^2, D = sqrt(w^2 + 4 a~^2 z^2),
+ *              r^2 = (w + D) / 2, r = sqrt(r^2), G = r^4 + a~^2 z^2, S = r^2 + a~^2,
+ *              f = 2 M r^3 / G, l = ((r x + a~ y) / S, (r y - a~ x) / S, z / r).
+ *  Hamiltonian H = 1/2 [-E^2 + p.p - f u^2] with u = E + l.p; E > 0 is constant along the ray.
+ *  Equations   xdot_i = p_i - f u l_i, pdot_i = 1/2 (d_i f) u^2 + f u (d_i l_j) p_j, with the
+ *              analytic gradients dr = (x r / D, y r / D, z S / (r D)),
+ *              d_i f = f (3 d_i r / r - (4 r^3 d_i r + 2 a~^2 z delta_iz) / G),
+ *              d_i l_x = (x d_i r + r delta_ix + a~ delta_iy) / S - l_x 2 r d_i r / S,
+ *              d_i l_y = (y d_i r + r delta_iy - a~ delta_ix) / S - l_y 2 r d_i r / S,
+ *              d_i l_z = delta_iz / r - z d_i r / r^2.
+ *  Initial data. A static observer at the origin with local photon energy 1 and unit direction n
+ *              (a ray's direction is normalised, n = d / sqrt((dx^2 + dy^2) + dz^2), and so is a
+ *              camera pixel's -- calculate_ray_direction's unit vector, formed with one operation
+ *              per rounding, goes through the same division again):
+ *              kappa = sqrt(1 - f), v = n + (kappa - 1)(l.n) l, k^t = 1 / kappa + f (l.v) / (1 - f),
+ *              p = v + f (k^t + l.v) l, E = kappa; H = 0 holds by construction. An origin with
+ *              f >= 1 or r <= r+ has no static observer: the camera and host-ray calls refuse it
+ *              before any HIP call, a device ray there gets RAY_ERROR with steps 0.
+ *  Step.       Classical RK4 on (x, p); h = time_step min(1, max(r / (8 M), 1 / 16)), r at the
+ *              step's start.
+ *  After each step, in this order, with p_old, p_new the two points, c = p_new - p_old and
+ *              seg = sqrt((cx^2 + cy^2) + cz^2):
+ *              1. any non-finite state component: RAY_ERROR;
+ *              2. with a disk: a crossing is (z_old > 0 and z_new <= 0) or (z_old < 0 and
+ *                 z_new >= 0); then t = z_old / (z_old - z_new), q = p_old + t c, a hit iff
+ *                 in^2 + a~^2 <= q_x^2 + q_y^2 <= out^2 + a~^2 (Boyer-Lindquist radius in [in, out]
+ *                 on the equator; both bounds formed once on the host): RAY_DISK, hit = (q_x, q_y,
+ *                 0), distance += t seg. The first hit wins;
+ *              3. r_new <= r+ = M + sqrt(M^2 - a~^2): RAY_HORIZON;
+ *              4. distance += seg; distance > max_ray_distance: RAY_MAX_DISTANCE;
+ *              5. steps >= max_integration_steps: RAY_MAX_STEPS (max_integration_steps == 0: at the
+ *                 origin, with steps 0).
+ *  Outputs     (bhrt_frame_soa): result; steps, the number of RK4 steps; hit_*, the last point or
+ *              the disk point; distance; sky_*, the exit chord c of a RAY_MAX_DISTANCE ray (other
+ *              rays' elements are not written); time_dilation must be NULL.
+ *  Colour.     The frame colour contract: the disk colour of (hit_x, hit_y),
+ *              BHRT_FLAG_DOPPLER reading the hitting segment's unit chord as d; black for the
+ *              horizon; every other ray the gradient, read on the unit EXIT CHORD's y if it is
+ *              RAY_MAX_DISTANCE -- which is what shows the lensing in the background -- else on n's
+ *              y. With BHRT_FLAG_SKY the sky-map rule applies unchanged (chord lookup, else n).
+ *  Determinism. No atomic in any output: a ray's outputs are a pure function of its inputs, the
+ *              same bits run to run, on any stream, in any row-shard split, and through the camera
+ *              and the ray-array entry points (one kernel instantiation serves them all).
+ *  Diagnostics (bhrt_kerr_diag, optional per-ray arrays, device or host as the call's outputs):
+ *              h_residual, the largest |(-E^2 + p.p - f u^2) / (E^2 + p.p + f u^2)| over the ray's
+ *              accepted points (the origin and every finite step end); lz_drift,
+ *              |(x p_y - y p_x)_end - (x p_y - y p_x)_0| at the last finite step end.
+ *  Refusals.   -1 with bhrt_last_error set and nothing written, each decided BEFORE ANY HIP CALL
+ *              (the current device's query aside): a NULL blackhole, config or output struct;
+ *              |spin| >= 1 or NaN; mass not finite or not > 0; time_step not finite or not > 0;
+ *              max_integration_steps < 0; a NaN max_ray_distance; a disk with NaN or negative
+ *              radii; time_dilation != NULL; rgb not given as all three channels; an origin
+ *              without a static observer (camera and host-ray calls); n <= 0, width or height < 1,
+ *              a bad row sharding; BHRT_FLAG_SKY without a map bound on this device. HIP failures
+ *              also return -1.
+ *  Statistics. bhrt_stats counts a launch as a trace launch: rays, iterations (RK4 steps), launches.
+ *  Not offered. The supersampled, adaptive, accumulator and path calls do not take this path; a
+ *              caller accumulates these frames through bhrt_accum_blend_device. */
+typedef struct {
+    double* h_residual;
+    double* lz_drift;
+} bhrt_kerr_diag;
+
+/* (A shard of) a camera frame into DEVICE arrays on hip_stream: asynchronous, no host wait; NULL
+ * is ordered like the legacy default stream, as for bhrt_render_frame_device. camera->use_offset
+ * and row shards are honoured. diag may be NULL. */
+int bhrt_kerr_frame_device(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                           const SimulationConfig* config, const bhrt_camera* camera, int width,
+                           int height, const bhrt_rows* rows, int flags,
+                           const bhrt_frame_soa* device_out, const bhrt_kerr_diag* device_diag,
+                           void* hip_stream);
+/* The whole frame into HOST arrays on the current device; returns when they are complete. */
+int bhrt_kerr_frame(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                    const SimulationConfig* config, const bhrt_camera* camera, int width, int height,
+                    int flags, const bhrt_frame_soa* host_out, const bhrt_kerr_diag* host_diag);
+/* n DEVICE rays (AoS Ray[n]) into DEVICE arrays, stream as above. */
+int bhrt_kerr_rays_device(const Ray* device_rays, int n, const BlackHoleParams* blackhole,
+                          const AccretionDiskParams* disk, const SimulationConfig* config, int flags,
+                          const bhrt_frame_soa* device_out, const bhrt_kerr_diag* device_diag,
+                          void* hip_stream);
+/* n HOST rays into HOST arrays on the current device; returns when they are complete. */
+int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
+                   const AccretionDiskParams* disk, const SimulationConfig* config, int flags,
+                   const bhrt_frame_soa* host_out, const bhrt_kerr_diag* host_diag);
+/* The initial data of one ray on the host, with the device's operations: state = (x, p), *E = E.
+ * 0, or -1 (nothing written) for a NULL argument, a bad blackhole as above, or an origin without
+ * a static observer. No HIP call. */
+int bhrt_kerr_ray_init(const BlackHoleParams* blackhole, const Vector3D* origin,
+                       const Vector3D* direction, double state[6], double* E);
+
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);
 

@@ -234,6 +234,12 @@ class SkyState(C.Structure):
                 ("device", C.c_int32)]
 
 
+class KerrDiag(C.Structure):
+    """bhrt_kerr_diag: optional per-ray arrays (device or host, as the call's outputs); 0 = not
+    produced."""
+    _fields_ = [("h_residual", C.c_void_p), ("lz_drift", C.c_void_p)]
+
+
 class ParticlesState(C.Structure):
     """bhrt_particles_state: the host-side state of a device-resident particle system."""
     _fields_ = [("count", C.c_int32), ("device", C.c_int32), ("updates", C.c_int64)]

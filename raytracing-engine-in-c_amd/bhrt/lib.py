@@ -120,6 +120,21 @@ _PROTOS = {
     "bhrt_sky_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p]),
     "bhrt_sky_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bhrt_kerr_frame_device": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.AccretionDiskParams),
+                                         _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
+                                         C.c_int, _P(abi.Rows), C.c_int, _P(abi.FrameSoA),
+                                         _P(abi.KerrDiag), C.c_void_p]),
+    "bhrt_kerr_frame": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.AccretionDiskParams),
+                                  _P(abi.SimulationConfig), _P(abi.Camera), C.c_int, C.c_int,
+                                  C.c_int, _P(abi.FrameSoA), _P(abi.KerrDiag)]),
+    "bhrt_kerr_rays_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                        _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                        C.c_int, _P(abi.FrameSoA), _P(abi.KerrDiag), C.c_void_p]),
+    "bhrt_kerr_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                 _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
+                                 _P(abi.FrameSoA), _P(abi.KerrDiag)]),
+    "bhrt_kerr_ray_init": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.Vector3D), _P(abi.Vector3D),
+                                     _P(C.c_double * 6), _P(C.c_double)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -586,6 +601,65 @@ def trace_paths(rays, bh, dk, cfg, method=abi.INTEGRATOR_RK4, max_positions=1001
     arrays["xyz"] = xyz
     arrays["count"] = count
     return arrays
+
+
+KERR_FIELDS = tuple(f for f in abi.SOA_FIELDS if f != "time_dilation")  # never produced here
+
+
+def _kerr_host_diag(n, diag):
+    if not diag:
+        return {}, None
+    arrays = {"h_residual": np.zeros(n), "lz_drift": np.zeros(n)}
+    return arrays, abi.KerrDiag(arrays["h_residual"].ctypes.data, arrays["lz_drift"].ctypes.data)
+
+
+def kerr_frame_device(bh, dk, cfg, cam, width, height, rows, flags, soa, diag=None, stream=None):
+    """bhrt_kerr_frame_device: (a shard of) a camera frame of physical Kerr geodesics into device
+    SoA buffers, asynchronous on a hipStream_t (int handle or None); diag an abi.KerrDiag of
+    device pointers or None."""
+    _check(load().bhrt_kerr_frame_device(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
+                                         _ptr(rows), flags, C.byref(soa), _ptr(diag),
+                                         C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_frame_device")
+
+
+def kerr_frame(bh, dk, cfg, cam, width, height, flags=0, fields=KERR_FIELDS, diag=False):
+    """bhrt_kerr_frame into host numpy arrays (with diag: h_residual and lz_drift as well)."""
+    arrays, soa = abi.alloc_soa(width * height, fields)
+    extra, kd = _kerr_host_diag(width * height, diag)
+    _check(load().bhrt_kerr_frame(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height, flags,
+                                  C.byref(soa), _ptr(kd)), "bhrt_kerr_frame")
+    arrays.update(extra)
+    return arrays
+
+
+def kerr_rays_device(rays_ptr, n, bh, dk, cfg, flags, soa, diag=None, stream=None):
+    """bhrt_kerr_rays_device: n device rays (AoS) into device SoA buffers on a hipStream_t."""
+    _check(load().bhrt_kerr_rays_device(C.c_void_p(rays_ptr), n, _ptr(bh), _ptr(dk), _ptr(cfg),
+                                        flags, C.byref(soa), _ptr(diag),
+                                        C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_rays_device")
+
+
+def kerr_rays(rays, bh, dk, cfg, flags=0, fields=KERR_FIELDS, diag=False):
+    """bhrt_kerr_rays: rays is a numpy array of abi.RAY_DTYPE; host numpy arrays back."""
+    rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+    arrays, soa = abi.alloc_soa(len(rays), fields)
+    extra, kd = _kerr_host_diag(len(rays), diag)
+    _check(load().bhrt_kerr_rays(rays.ctypes.data, len(rays), _ptr(bh), _ptr(dk), _ptr(cfg), flags,
+                                 C.byref(soa), _ptr(kd)), "bhrt_kerr_rays")
+    arrays.update(extra)
+    return arrays
+
+
+def kerr_ray_init(bh, origin, direction):
+    """bhrt_kerr_ray_init: (state [6] = (x, p), E) of one ray, on the host."""
+    state = (C.c_double * 6)()
+    E = C.c_double()
+    o, d = abi.v3(*origin), abi.v3(*direction)
+    _check(load().bhrt_kerr_ray_init(_ptr(bh), C.byref(o), C.byref(d), C.byref(state), C.byref(E)),
+           "bhrt_kerr_ray_init")
+    return np.array(state[:]), E.value
 
 
 def set_claim_order(d_order_ptr, n):

@@ -8,7 +8,8 @@
  *   host_frames.c  host-buffer frames in flight, readback, bhrt_trace_rays
  *   batch.c        trace_ray / trace_rays_batch: the pipelined chunks
  *   dropin.c       integrate_photon_path, trace_pixel, the bh_* context API
- *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c, sky.c
+ *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c, sky.c,
+ *   kerr.c
  *                  features with launchers of their own
  */
 #ifndef BHRT_HOST_H

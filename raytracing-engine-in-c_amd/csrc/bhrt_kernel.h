@@ -317,6 +317,31 @@ int bhrt_launch_particles_scatter(const Particle* d_particles, int count, const 
 int bhrt_launch_sky(const bhrt_sky_k* sky, const double* d_dirs, int n, double* d_rgb,
                     void* stream);
 
+/* Physical geodesics (kerr.c; kerr.hip k_kerr; the rule: include/bhrt_api.h "Physical
+ * geodesics"). The launch's bhrt_kparams carries the source (src, n, rays or cam -- basis, image
+ * plane, row shard and cam.pos, the shared origin), the outputs, the control block (ctl[0]: the
+ * claim counter, ctl[1..2]: rays and RK4 steps, ctl[8..9]: the execution window) and what the
+ * colour reads (sc.flags, sc.rs, sc.has_disk, sc.disk_in / disk_out / disk_tscale, sky); this
+ * block the integration's constants, each formed once on the host. */
+typedef struct {
+    double M, two_m;      /* mass, 2 M                                                      */
+    double a, a2;         /* a~ = -(spin * mass), a~^2                                       */
+    double r_plus;        /* M + sqrt(M^2 - a~^2)                                            */
+    double eight_m;       /* 8 M: the step size reads r / (8 M)                             */
+    double dt, max_dist;  /* time_step, max_ray_distance                                    */
+    double disk_lo, disk_hi; /* in^2 + a~^2, out^2 + a~^2: the bounds of q_x^2 + q_y^2      */
+    int max_steps, has_disk;
+    int tiles_x, ntiles;  /* camera frames: 8x8 tiles per row of tiles, tiles in the shard   */
+    int nrows;            /* camera frames: the shard's rows                                 */
+    double* h_residual;   /* bhrt_kerr_diag, device [n] or NULL                              */
+    double* lz_drift;
+} bhrt_kerr_k;
+
+/* kerr.hip; asynchronous on `stream`, ev0/ev1 (hipEvent_t, may be NULL) recorded around the
+ * kernel; returns 0 or a hipError_t value */
+int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, void* stream, void* ev0,
+                     void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */

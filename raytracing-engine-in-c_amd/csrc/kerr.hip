@@ -1,0 +1,330 @@
+// kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: the kernel
+// k_kerr and its launcher (the rule: include/bhrt_api.h "Physical geodesics"; tests/kerr_rule.py
+// restates it in numpy; the host side is kerr.c).
+//
+// One lane per ray, FP64, fixed-step RK4 on (x, p), no LDS. A wavefront claims 64 rays at a time
+// from the launch's claim counter -- an 8x8 pixel tile of a camera frame, so that its rays live
+// alike, or 64 consecutive rays of an array -- and runs them until the last has ended; there is no
+// refill of single lanes. Each stage forms the reciprocals of D, r, G and S once; the geometry at
+// a step's end point serves the horizon test, the next step's size and the next step's first
+// stage, so a step costs four geometry evaluations.
+//
+// ONE instantiation serves camera frames and ray arrays, with and without a disk, a sky map or
+// the diagnostics (wave-uniform branches outside the stages): a ray's arithmetic is compiled once,
+// so its outputs are the same bits through every entry point. No atomic touches an output; the
+// claim counter and the statistics are the only atomics.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "bhrt_kernel.h"
+#include "kerr_init.h"
+
+namespace {
+
+using Scene = bhrt_scene_k;
+
+#include "bhrt_colour.h"
+
+constexpr double kDblMax = 1.79769313486231570815e+308;
+
+struct Geom {
+    double r, ir, iD, iG, iS, S, f, lx, ly, lz;
+};
+
+// the geometry at (x, y, z): two square roots, four reciprocals
+__device__ __forceinline__ Geom geom(double x, double y, double z, const bhrt_kerr_k& k) {
+    Geom g;
+    const double z2 = z * z;
+    const double rho2 = (x * x + y * y) + z2;
+    const double w = rho2 - k.a2;
+    const double az2 = k.a2 * z2;
+    const double D = sqrt(w * w + 4.0 * az2);
+    const double r2 = 0.5 * (w + D);
+    g.r = sqrt(r2);
+    const double G = r2 * r2 + az2;
+    g.S = r2 + k.a2;
+    g.ir = 1.0 / g.r;
+    g.iD = 1.0 / D;
+    g.iG = 1.0 / G;
+    g.iS = 1.0 / g.S;
+    g.f = k.two_m * (g.r * r2) * g.iG;
+    g.lx = (g.r * x + k.a * y) * g.iS;
+    g.ly = (g.r * y - k.a * x) * g.iS;
+    g.lz = z * g.ir;
+    return g;
+}
+
+// xdot_i = p_i - f u l_i, pdot_i = 1/2 (d_i f) u^2 + f u (d_i l_j) p_j with the analytic gradients;
+// the terms of d_i l_j p_j that carry d_i r are gathered into one factor (Ap)
+__device__ __forceinline__ void deriv(const Geom& g, double x, double y, double z, double px,
+                                      double py, double pz, double E, const bhrt_kerr_k& k,
+                                      double (&d)[6]) {
+    const double u = E + ((g.lx * px + g.ly * py) + g.lz * pz);
+    const double fu = g.f * u;
+    d[0] = px - fu * g.lx;
+    d[1] = py - fu * g.ly;
+    d[2] = pz - fu * g.lz;
+    const double rD = g.r * g.iD;
+    const double drx = x * rD, dry = y * rD, drz = z * g.S * (g.ir * g.iD);
+    const double r3 = g.r * g.r * g.r;
+    const double q = g.f * (3.0 * g.ir - 4.0 * r3 * g.iG);
+    const double hu2 = 0.5 * (u * u);
+    const double t = 2.0 * g.r * g.iS;
+    const double A = x * g.iS - g.lx * t, B = y * g.iS - g.ly * t, Cz = -z * (g.ir * g.ir);
+    const double Ap = (A * px + B * py) + Cz * pz;
+    d[3] = hu2 * (q * drx) + fu * (drx * Ap + (g.r * px - k.a * py) * g.iS);
+    d[4] = hu2 * (q * dry) + fu * (dry * Ap + (k.a * px + g.r * py) * g.iS);
+    d[5] = hu2 * (q * drz - g.f * (2.0 * k.a2 * z) * g.iG) + fu * (drz * Ap + g.ir * pz);
+}
+
+__device__ __forceinline__ bool finite6(const double (&y)[6]) {
+    return fabs(y[0]) <= kDblMax && fabs(y[1]) <= kDblMax && fabs(y[2]) <= kDblMax &&
+           fabs(y[3]) <= kDblMax && fabs(y[4]) <= kDblMax && fabs(y[5]) <= kDblMax;
+}
+
+// |(-E^2 + p.p - f u^2) / (E^2 + p.p + f u^2)| at a point whose geometry is g
+__device__ __forceinline__ double h_residual(const Geom& g, const double (&y)[6], double E) {
+    const double u = E + ((g.lx * y[3] + g.ly * y[4]) + g.lz * y[5]);
+    const double pp = (y[3] * y[3] + y[4] * y[4]) + y[5] * y[5];
+    const double fu2 = g.f * (u * u);
+    return fabs(((pp - E * E) - fu2) / ((E * E + pp) + fu2));
+}
+
+// the direction of shard pixel (px, row j of the shard): calculate_ray_direction's mapping, one
+// operation per rounding (tests/kerr_rule.py camera_dirs forms the same bits)
+__device__ __forceinline__ void camera_dir(const bhrt_camera_k& cm, int px, int j, double (&d)[3]) {
+#pragma clang fp contract(off)
+    int py = j;
+    if (cm.rows.num_shards > 1) {
+        const int B = cm.rows.row_block, jb = j / B;
+        py = (jb * cm.rows.num_shards + cm.rows.shard) * B + (j - jb * B);
+    }
+    const double ndcx = (2.0 * (((double)px + cm.off_x) / (double)cm.width) - 1.0) * cm.plane_w;
+    const double ndcy = (1.0 - 2.0 * (((double)py + cm.off_y) / (double)cm.height)) * cm.plane_h;
+    const double v[3] = {(cm.fwd[0] + cm.right[0] * ndcx) + cm.up[0] * ndcy,
+                         (cm.fwd[1] + cm.right[1] * ndcx) + cm.up[1] * ndcy,
+                         (cm.fwd[2] + cm.right[2] * ndcx) + cm.up[2] * ndcy};
+    bhrt_kerr_unit(v, d);
+}
+
+// The launch parameters as an opaque pointer into the kernel argument segment (k_kerr's first
+// argument starts it): the fields read through it -- the camera at a ray's set-up, the output
+// pointers, the colour's constants and the sky map at its exit -- are loaded where they are used
+// instead of being held in scalar registers across the steps.
+typedef const __attribute__((address_space(4))) bhrt_kparams kparams_as4;
+__device__ __forceinline__ const bhrt_kparams& in_kernarg(const bhrt_kparams&) {
+    kparams_as4* p = (kparams_as4*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const bhrt_kparams*)p;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
+    unsigned long long s = v;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+
+__global__ __launch_bounds__(64) void k_kerr(const bhrt_kparams kp, const bhrt_kerr_k kk) {
+    const int lane = threadIdx.x;
+    const bhrt_kparams& kc = in_kernarg(kp);
+    const bool camera = kp.src == BHRT_SRC_CAMERA;
+    const bool diag = kk.h_residual != nullptr || kk.lz_drift != nullptr;
+    const unsigned long long units =
+        camera ? (unsigned long long)kk.ntiles : ((unsigned long long)kp.n + 63ull) / 64ull;
+    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    unsigned n_rays = 0, n_steps = 0;
+    for (;;) {
+        unsigned long long unit = 0;
+        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
+        unit = __shfl(unit, 0);
+        if (unit >= units) break;
+        // the lane's ray: id i (the output element), origin and direction
+        int i;
+        bool live;
+        double o[3], dir[3];
+        if (camera) {
+            const int ty = (int)unit / kk.tiles_x, tx = (int)unit - ty * kk.tiles_x;
+            const int px = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+            live = px < kc.cam.width && j < kk.nrows;
+            i = j * kc.cam.width + px;
+            o[0] = kc.cam.pos[0];
+            o[1] = kc.cam.pos[1];
+            o[2] = kc.cam.pos[2];
+            camera_dir(kc.cam, live ? px : 0, live ? j : 0, dir);
+        } else {
+            i = (int)unit * 64 + lane;
+            live = i < kp.n;
+            const Ray ray = kc.rays[live ? i : 0];
+            o[0] = ray.origin.x;
+            o[1] = ray.origin.y;
+            o[2] = ray.origin.z;
+            dir[0] = ray.direction.x;
+            dir[1] = ray.direction.y;
+            dir[2] = ray.direction.z;
+        }
+        double nv[3], l0[3], p0[3], f0, E;
+        bhrt_kerr_unit(dir, nv);
+        const bool observer =
+            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
+        bhrt_kerr_photon(f0, l0, nv, p0, &E);
+        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
+        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+        int steps = 0;
+        double dist = 0.0, cx = 0.0, cy = 0.0, cz = 0.0;
+        Geom g = geom(y[0], y[1], y[2], kk);
+        const double lz0 = y[0] * y[4] - y[1] * y[3];
+        double hres = 0.0, lzd = 0.0;
+        if (diag && observer) hres = h_residual(g, y, E);
+        bool run = live && res < 0;
+        while (__ballot(run) != 0ull) {
+            if (run) {
+                const double h = kk.dt * fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
+                const double hh = 0.5 * h;
+                double k1[6], k2[6], k3[6], k4[6], s[6];
+                deriv(g, y[0], y[1], y[2], y[3], y[4], y[5], E, kk, k1);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k1[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k2[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + h * k3[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
+                const double h6 = h / 6.0;
+                double yn[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++)
+                    yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
+                steps++;
+                cx = yn[0] - y[0];
+                cy = yn[1] - y[1];
+                cz = yn[2] - y[2];
+                const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
+                const Geom gn = geom(yn[0], yn[1], yn[2], kk);
+                const double zo = y[2], zn = yn[2];
+                if (!finite6(yn)) {  // 1. a non-finite state
+                    res = RAY_ERROR;
+                } else {
+                    if (diag) {  // (the accepted point: before a disk hit replaces it)
+                        hres = fmax(hres, h_residual(gn, yn, E));
+                        lzd = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - lz0);
+                    }
+                    if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
+                        const double t = zo / (zo - zn);  // 2. the disk
+                        const double qx = y[0] + t * cx, qy = y[1] + t * cy;
+                        const double s2 = qx * qx + qy * qy;
+                        if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+                            res = RAY_DISK;
+                            yn[0] = qx;
+                            yn[1] = qy;
+                            yn[2] = 0.0;
+                            dist += t * seg;
+                        }
+                    }
+                    if (res < 0) {
+                        if (gn.r <= kk.r_plus) {  // 3. the horizon
+                            res = RAY_HORIZON;
+                        } else {
+                            dist += seg;  // 4. the distance
+                            if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
+                            else if (steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 5.
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 6; c++) y[c] = yn[c];
+                g = gn;
+                run = res < 0;
+            }
+        }
+        if (!live) continue;
+        n_rays++;
+        n_steps += (unsigned)steps;
+        const bhrt_frame_soa& out = kc.out;
+        if (out.result) out.result[i] = res;
+        if (out.steps) out.steps[i] = steps;
+        if (out.hit_x) out.hit_x[i] = y[0];
+        if (out.hit_y) out.hit_y[i] = y[1];
+        if (out.hit_z) out.hit_z[i] = y[2];
+        if (out.distance) out.distance[i] = dist;
+        if (res == RAY_MAX_DISTANCE) {
+            if (out.sky_x) out.sky_x[i] = cx;
+            if (out.sky_y) out.sky_y[i] = cy;
+            if (out.sky_z) out.sky_z[i] = cz;
+        }
+        if (kk.h_residual) kk.h_residual[i] = hres;
+        if (kk.lz_drift) kk.lz_drift[i] = lzd;
+        if (out.rgb_r || out.rgba32f || out.rgba8) {
+            // the unit chord of the last segment: the Doppler direction of a disk hit, and what
+            // the gradient reads for a ray that left the scene; every other ray reads n
+            double uc[3];
+            const double c3[3] = {cx, cy, cz};
+            bhrt_kerr_unit(c3, uc);
+            double r, gg, b;
+            if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_DISK && res != RAY_HORIZON) {
+                // the sky-map rule: the exit chord of a ray that left the scene if it counts
+                // (finite, squared length > 0), else n. Inlined here, not colour_of_sky's call:
+                // that function returns through memory, and this kernel has one instantiation,
+                // so there is no second copy of the iterations to keep in step with
+                const double l2 = (cx * cx + cy * cy) + cz * cz;
+                const bool take = res == RAY_MAX_DISTANCE && fabs(cx) <= kDblMax &&
+                                  fabs(cy) <= kDblMax && fabs(cz) <= kDblMax && l2 > 0.0;
+                sky_lookup(kc.sky, take ? cx : nv[0], take ? cy : nv[1], take ? cz : nv[2], r, gg,
+                           b);
+            } else {
+                const bool chord = res == RAY_DISK || res == RAY_MAX_DISTANCE;
+                colour_of(kc.sc, res, y[0], y[1], chord ? uc[0] : nv[0], chord ? uc[1] : nv[1],
+                          chord ? uc[2] : nv[2], r, gg, b);
+            }
+            store_colour(out, i, r, gg, b);
+        }
+    }
+    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
+    if (lane == 0) {
+        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
+        if (s0) atomicAdd(kp.ctl + 1, s0);
+        if (s1) atomicAdd(kp.ctl + 2, s1);
+    }
+}
+
+// resident one-wave workgroups of k_kerr per device (a pure function of the device: concurrent
+// first calls store the same value)
+constexpr int kMaxDev = 64;
+std::atomic<int> g_blocks[kMaxDev];
+
+int resident_blocks() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
+    int blocks = g_blocks[dev].load(std::memory_order_relaxed);
+    if (blocks == 0) {
+        int cus = 0, per_cu = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            cus <= 0)
+            cus = 256;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, reinterpret_cast<const void*>(&k_kerr), 64, 0);
+        if (per_cu <= 0) per_cu = 1;
+        blocks = cus * per_cu;
+        g_blocks[dev].store(blocks, std::memory_order_relaxed);
+    }
+    return blocks;
+}
+
+}  // namespace
+
+extern "C" int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, void* stream,
+                                void* ev0, void* ev1) {
+    if (kp->n <= 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
+    const long units = kp->src == BHRT_SRC_CAMERA ? (long)kk->ntiles : ((long)kp->n + 63) / 64;
+    long blocks = resident_blocks();
+    if (blocks > units) blocks = units;
+    if (e0) (void)hipEventRecord(e0, st);
+    k_kerr<<<(unsigned)blocks, 64, 0, st>>>(*kp, *kk);
+    if (e1) (void)hipEventRecord(e1, st);
+    return (int)hipGetLastError();
+}

@@ -1,0 +1,333 @@
+"""Physical geodesics (bhrt_kerr_*) without a GPU: the symbols, the header's rule, the numpy rule
+(kerr_rule.py) against the analytic critical impact parameters and its own handedness and
+condition, the host scalar form against the rule, the refusals that are decided before any HIP
+call, and the host code on simulated devices under ASan+UBSan (a stand-alone program; nothing is
+loaded into Python under a sanitizer). The rule is stated in include/bhrt_api.h."""
+import ctypes as C
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from bhrt import abi, lib
+from host_sources import host_core, host_feature
+import kerr_rule as kr
+
+CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
+FAKE = os.path.join(ROOT, "tests", "fakehip")
+ENTRIES = ("bhrt_kerr_frame_device", "bhrt_kerr_frame", "bhrt_kerr_rays_device", "bhrt_kerr_rays",
+           "bhrt_kerr_ray_init")
+WRAPPERS = ("kerr_frame_device", "kerr_frame", "kerr_rays_device", "kerr_rays", "kerr_ray_init")
+
+
+def test_symbols_prototypes_and_the_diag_struct():
+    L = lib.load()
+    for name in ENTRIES:
+        assert hasattr(L, name), name
+        assert name in lib._PROTOS, name
+    for name in WRAPPERS:
+        assert callable(getattr(lib, name)), name
+    assert C.sizeof(abi.KerrDiag) == 16
+    assert (abi.KerrDiag.h_residual.offset, abi.KerrDiag.lz_drift.offset) == (0, 8)
+    assert "time_dilation" not in lib.KERR_FIELDS
+    header = open(os.path.join(ROOT, "include", "bhrt_api.h")).read()
+    for name in ENTRIES:
+        assert re.search(r"\b%s\(" % name, header), name
+    assert re.search(r"double\* h_residual;\s*double\* lz_drift;\s*\} bhrt_kerr_diag;", header)
+
+
+def test_header_states_the_rule():
+    header = " ".join(open(os.path.join(ROOT, "include", "bhrt_api.h")).read().split())
+    header = header.replace(" * ", " ")   # (comment continuation marks)
+    for phrase in ("Physical geodesics", "THE RULE", "Time reversal", "a~ = -(spin mass)",   # (" * " is dropped above)
+                   "D = sqrt(w^2 + 4 a~^2 z^2)", "r^2 = (w + D) / 2", "G = r^4 + a~^2 z^2",
+                   "f = 2 M r^3 / G", "(r x + a~ y) / S, (r y - a~ x) / S, z / r",
+                   "H = 1/2 [-E^2 + p.p - f u^2]", "u = E + l.p", "xdot_i = p_i - f u l_i",
+                   "pdot_i = 1/2 (d_i f) u^2 + f u (d_i l_j) p_j", "z S / (r D)",
+                   "kappa = sqrt(1 - f)", "v = n + (kappa - 1)(l.n) l",
+                   "k^t = 1 / kappa + f (l.v) / (1 - f)", "p = v + f (k^t + l.v) l", "E = kappa",
+                   "f >= 1 or r <= r+", "RAY_ERROR with steps 0", "Classical RK4",
+                   "h = time_step min(1, max(r / (8 M), 1 / 16))", "in this order",
+                   "t = z_old / (z_old - z_new)", "in^2 + a~^2 <= q_x^2 + q_y^2 <= out^2 + a~^2",
+                   "The first hit wins", "r+ = M + sqrt(M^2 - a~^2)", "time_dilation must be NULL",
+                   "unit EXIT CHORD", "No atomic in any output", "h_residual", "lz_drift",
+                   "BEFORE ANY HIP CALL", "|spin| >= 1 or NaN", "bhrt_accum_blend_device"):
+        assert phrase in header, phrase
+
+
+def test_host_core_does_not_name_the_launcher():
+    for f in host_core():
+        assert "bhrt_launch_kerr" not in open(f).read(), f
+    assert os.path.join(CSRC, "kerr.c") in host_feature()
+    assert os.path.join(CSRC, "kerr.c") not in host_core()
+    for f in ("kerr.c", "kerr.hip", "bhrt_kernel.h"):
+        assert "bhrt_launch_kerr(" in open(os.path.join(CSRC, f)).read(), f
+    # the colour and sky functions are shared through one header, not copied
+    for f in ("geodesic.hip", "kerr.hip"):
+        text = open(os.path.join(CSRC, f)).read()
+        assert '#include "bhrt_colour.h"' in text and "void sky_lookup(" not in text, f
+
+
+# ---- the rule against closed forms ----
+# the rule's own relative error on each critical impact parameter, measured with the tests'
+# step and distance (time_step 0.25, max distance 60, rays from x = 20): the bound is 10x that
+RULE_ERROR = {(0.0, 1): 1.09e-6, (0.0, -1): 1.09e-6, (0.5, 1): 1.74e-6, (0.5, -1): 1.26e-6,
+              (0.9, 1): 2.81e-6, (0.9, -1): 2.07e-5}
+
+
+@pytest.mark.parametrize("spin", [0.0, 0.5, 0.9])
+@pytest.mark.parametrize("side", [1, -1])
+def test_rule_critical_impact_parameters_vs_analytic(spin, side):
+    """Bisected capture / escape boundary of equatorial rays from (20, 0, 0) against
+    b = -(r^3 - 3 M r^2 + a^2 r + a^2 M) / (a (r - M)) at r = 2 M (1 + cos(2/3 acos(-+a / M)))
+    with a = a~ (3 sqrt(3) M at spin 0). Measured, b = L_z / E of the rule (analytic; relative
+    error): spin 0: +-5.196147 (5.196152; 1.08e-6); spin 0.5: n_y > 0 6.138145 (6.138156;
+    1.74e-6), n_y < 0 -4.096262 (-4.096267; 1.26e-6); spin 0.9: n_y > 0 6.832300 (6.832319;
+    2.81e-6), n_y < 0 -2.844363 (-2.844421; 2.06e-5 -- the orbit at r = 1.558 M, where the step
+    is shortest). Asserted at 10x these."""
+    b, width = kr.critical_angle_b(spin, side)
+    want = kr.analytic_b(spin, b)
+    err = abs(b - want) / abs(want)
+    print(f"spin {spin} side {side:+d}: b {b:.7f} analytic {want:.7f} rel {err:.3e} "
+          f"(bracket {width:.1e})")
+    assert width < 1e-9
+    assert err <= 10.0 * RULE_ERROR[(spin, side)], (b, want, err)
+
+
+def test_rule_handedness():
+    """Spin > 0 about +z, seen from (20, 0, 0): the hole turns toward the observer on the y < 0
+    side. The prograde edge, |b| = 2.84 at spin 0.9, is on the n_y < 0 side, the retrograde one,
+    6.83, on n_y > 0."""
+    b_neg, _ = kr.critical_angle_b(0.9, -1)
+    b_pos, _ = kr.critical_angle_b(0.9, 1)
+    assert abs(abs(b_neg) - 2.8444) < 1e-3 and b_neg < 0.0
+    assert abs(abs(b_pos) - 6.8323) < 1e-3 and b_pos > 0.0
+    # and it flips with the spin's sign
+    o = np.tile(kr.FAN_ORIGIN, (2, 1))
+    s = 4.0 / 20.0   # |b| about 4: between the two edges
+    d = np.array([[-math.sqrt(1 - s * s), -s, 0.0], [-math.sqrt(1 - s * s), s, 0.0]])
+    up = kr.trace(o, d, 0.9, 1.0, None, kr.SCENE_DT, kr.SCENE_DIST, kr.SCENE_STEPS)["result"]
+    down = kr.trace(o, d, -0.9, 1.0, None, kr.SCENE_DT, kr.SCENE_DIST, kr.SCENE_STEPS)["result"]
+    assert up.tolist() == [kr.MAX_DISTANCE, kr.HORIZON]
+    assert down.tolist() == [kr.HORIZON, kr.MAX_DISTANCE]
+
+
+def test_rule_gradients_are_the_hamiltonians():
+    """pdot = -dH/dx of the rule's analytic gradients against central differences."""
+    rng = np.random.default_rng(5)
+    a, M = -0.9, 1.0
+    for _ in range(20):
+        x = rng.normal(size=3) * 4.0
+        if kr.geometry(*x, a, M)["r"] < 1.6:
+            continue
+        p, E = rng.normal(size=3), 0.9
+
+        def H(q):
+            num, _ = kr.hamiltonian_parts(q[0], q[1], q[2], p[0], p[1], p[2], E, a, M)
+            return 0.5 * num
+
+        _, pd = kr.rhs(x[0], x[1], x[2], p[0], p[1], p[2], E, a, M)
+        for i in range(3):
+            e = np.zeros(3)
+            e[i] = 1e-6
+            fd = -(H(x + e) - H(x - e)) / 2e-6
+            assert abs(fd - pd[i]) <= 1e-7 * max(1.0, abs(fd)), (x, i, fd, pd[i])
+
+
+# ---- the host scalar form ----
+def test_ray_init_is_the_rules_initial_data():
+    rng = np.random.default_rng(11)
+    worst = worst_h = 0.0
+    for spin in (0.0, 0.5, 0.9, -0.7):
+        for mass in (1.0, 2.5):
+            bh = abi.black_hole(mass, abs(spin))
+            bh.spin = spin
+            a = kr.spin_a(spin, mass)
+            for _ in range(25):
+                o = kr.normalise(rng.normal(size=3)) * mass * rng.uniform(3.0, 40.0)
+                d = rng.normal(size=3) * 3.0
+                state, E = lib.kerr_ray_init(bh, o, d)
+                p, e, _ = kr.initial_data(o, kr.normalise(d), a, mass)
+                assert np.array_equal(state[:3], o)
+                rel = max(np.abs(state[3:] - p).max() / np.abs(p).max(), abs(E - e) / e)
+                worst = max(worst, rel)
+                assert rel <= 1e-14, (spin, mass, o, d, rel)
+                # H = 0 at the start, to 1e-15: H = 1/2 [-E^2 + p.p - f u^2] itself, whose terms
+                # are of order 1 for these observers (r >= 3 M: E in [0.57, 1), |p| below 2.2)
+                num, _ = kr.hamiltonian_parts(*state[:3], *state[3:], E, a, mass)
+                worst_h = max(worst_h, abs(0.5 * num))
+                assert abs(0.5 * num) <= 1e-15, (spin, mass, o, d, 0.5 * num)
+    print(f"ray_init vs the rule: worst relative difference {worst:.2e}, worst |H| {worst_h:.2e}")
+
+
+def test_refusals_without_a_device():
+    """Every refusal is decided before any HIP call: -1, its message, nothing written -- on a
+    machine without a GPU too. (tests/fakehip/kerr_driver.c counts the HIP calls: zero.)"""
+    L = lib.load()
+    bh, dk, cfg = kr.scene(0.9, (2.4, 12.0))
+    cam = kr.camera()
+    n = 48 * 27
+    arrays, soa = abi.alloc_soa(n, lib.KERR_FIELDS)
+    for a in arrays.values():
+        a[...] = 7
+    rays = np.zeros(n, dtype=abi.RAY_DTYPE)
+    rays["origin"] = (0.0, -18.0, 4.0)
+    rays["direction"] = (0.0, 1.0, 0.0)
+
+    def frame(bh=bh, dk=dk, cfg=cfg, cam=cam, W=48, H=27, flags=0, soa=soa):
+        return L.bhrt_kerr_frame(lib._ptr(bh), lib._ptr(dk), lib._ptr(cfg), lib._ptr(cam), W, H,
+                                 flags, lib._ptr(soa), None)
+
+    def frame_dev(bh=bh, dk=dk, cfg=cfg, cam=cam, W=48, H=27, flags=0, soa=soa, rows=None):
+        return L.bhrt_kerr_frame_device(lib._ptr(bh), lib._ptr(dk), lib._ptr(cfg), lib._ptr(cam), W,
+                                        H, lib._ptr(rows), flags, lib._ptr(soa), None, None)
+
+    def rays_host(bh=bh, dk=dk, cfg=cfg, flags=0, soa=soa, r=rays, count=n, **_):
+        return L.bhrt_kerr_rays(r.ctypes.data if r is not None else None, count, lib._ptr(bh),
+                                lib._ptr(dk), lib._ptr(cfg), flags, lib._ptr(soa), None)
+
+    def rays_dev(bh=bh, dk=dk, cfg=cfg, flags=0, soa=soa, r=rays, count=n, **_):
+        return L.bhrt_kerr_rays_device(r.ctypes.data if r is not None else None, count,
+                                       lib._ptr(bh), lib._ptr(dk), lib._ptr(cfg), flags,
+                                       lib._ptr(soa), None, None)
+
+    def every(message, **kw):
+        for call in (frame, frame_dev, rays_host, rays_dev):
+            assert call(**kw) == -1, (call.__name__, kw)
+            assert lib.last_error().startswith("kerr:") or "sky" in lib.last_error()
+            assert message in lib.last_error(), (call.__name__, lib.last_error())
+
+    def changed(obj, **fields):
+        c = type(obj).from_buffer_copy(obj)
+        for k, v in fields.items():
+            setattr(c, k, v)
+        return c
+
+    every("NULL", bh=None)
+    every("NULL", cfg=None)
+    every("NULL", soa=None)
+    for spin in (1.0, -1.0, 2.0, math.nan, math.inf):
+        every("spin", bh=changed(bh, spin=spin))
+    for mass in (0.0, -1.0, math.nan, math.inf):
+        every("mass", bh=changed(bh, mass=mass))
+    for step in (0.0, -0.1, math.nan, math.inf):
+        every("time_step", cfg=changed(cfg, time_step=step))
+    every("max_integration_steps", cfg=changed(cfg, max_integration_steps=-1))
+    every("max_ray_distance", cfg=changed(cfg, max_ray_distance=math.nan))
+    for radii in (dict(inner_radius=math.nan), dict(outer_radius=math.nan),
+                  dict(inner_radius=-1.0), dict(outer_radius=-2.0)):
+        every("disk radii", dk=changed(dk, **radii))
+    every("time_dilation", soa=changed(soa, time_dilation=arrays["hit_x"].ctypes.data))
+    every("rgb_r/g/b", soa=changed(soa, rgb_b=None))
+    every("no sky map is bound", flags=abi.BHRT_FLAG_SKY)
+    for origin in ((0.5, 0.0, 0.0), (1.9, 0.0, 0.0), (math.nan, 0.0, 0.0)):
+        bad = changed(cam, position=abi.v3(*origin))
+        assert frame(cam=bad) == -1 and "no static observer" in lib.last_error()
+        assert frame_dev(cam=bad) == -1 and "no static observer" in lib.last_error()
+        r = rays.copy()
+        r["origin"][5] = origin
+        assert rays_host(r=r) == -1 and "of ray 5" in lib.last_error()
+    assert frame(cam=None) == -1 and frame_dev(cam=None) == -1 and "camera" in lib.last_error()
+    assert frame(W=0) == -1 and frame_dev(H=-2) == -1 and "invalid size" in lib.last_error()
+    assert frame_dev(rows=abi.Rows(0, 0, 2)) == -1 and "row sharding" in lib.last_error()
+    assert frame_dev(rows=abi.Rows(8, 2, 2)) == -1 and "row sharding" in lib.last_error()
+    for count in (0, -1):
+        assert rays_host(count=count) == -1 and rays_dev(count=count) == -1
+        assert "at least 1" in lib.last_error()
+    assert rays_host(r=None) == -1 and rays_dev(r=None) == -1 and "rays" in lib.last_error()
+    for a in arrays.values():
+        assert (a == 7).all()
+    with pytest.raises(lib.BhrtError, match="spin"):
+        lib.kerr_frame(changed(bh, spin=1.0), dk, cfg, cam, 8, 8)
+    with pytest.raises(lib.BhrtError, match="no static observer"):
+        lib.kerr_ray_init(bh, (1.0, 0.5, 0.0), (1.0, 0.0, 0.0))
+
+
+# ---- the rule's condition on the test frames ----
+def test_rule_knife_edge_set_of_the_six_frames():
+    """Over the six frames, at most 0.5% of the rule's rays change class or step count under a
+    +-1e-9 direction perturbation (the knife-edge set the GPU comparison leaves out). Measured: 0
+    of 7857 rays; steps per frame 264189..277126, longest ray 309 steps, H residual at most
+    4.8e-5, L_z drift at most 2.0e-5, amplification of the perturbation into the hit point at
+    most 1.2e4."""
+    rays = edge = 0
+    for spin, disk in kr.SCENES:
+        for W, H in kr.FRAME_SIZES:
+            base = kr.frame_rule(spin, disk, W, H)
+            k = kr.knife_edge(spin, disk, W, H)
+            rays += len(k)
+            edge += int(k.sum())
+            counts = np.bincount(base["result"], minlength=6)
+            print(f"spin {spin} {W}x{H}: {int(base['steps'].sum())} steps, longest "
+                  f"{int(base['steps'].max())}, classes {counts.tolist()}, knife-edge {int(k.sum())}, "
+                  f"H residual {base['h_residual'].max():.2e}, L_z drift {base['lz_drift'].max():.2e}")
+            # every frame shows all three classes the scenes are built for
+            assert counts[kr.HORIZON] > 20 and counts[kr.DISK] > 100 and counts[kr.MAX_DISTANCE] > 500
+            assert counts[kr.ERROR] == 0 and counts[kr.MAX_STEPS] == 0
+            assert base["h_residual"].max() < 1e-4 and base["lz_drift"].max() < 1e-4
+    assert edge <= 0.005 * rays, (edge, rays)
+
+
+def test_rule_edge_cases():
+    """max_integration_steps == 0 ends at the origin; a short distance budget ends by distance
+    with the chord as the last segment; an origin without an observer is RAY_ERROR with steps 0;
+    the disk's bounds are BL radii: in^2 + a~^2 <= x^2 + y^2 on the equator."""
+    o = np.array([[0.0, -18.0, 4.0], [1.5, 0.0, 0.0]])
+    d = np.array([[0.0, 1.0, 0.0], [1.0, 0.0, 0.0]])
+    tr = kr.trace(o, d, 0.9, 1.0, None, 0.25, 60.0, 0)
+    assert tr["result"].tolist() == [kr.MAX_STEPS, kr.ERROR] and tr["steps"].tolist() == [0, 0]
+    assert np.array_equal(tr["hit"], o) and (tr["distance"] == 0.0).all()
+    tr = kr.trace(o[:1], d[:1], 0.9, 1.0, None, 0.25, 1.0, 2000)
+    assert tr["result"][0] == kr.MAX_DISTANCE and tr["steps"][0] == 5 and tr["distance"][0] > 1.0
+    assert np.allclose(tr["chord"][0], [0.0, 0.25, 0.0], atol=0.02)   # (dx/dlambda is not 1)
+    # straight down onto the equator from just above it, disk of BL radii [5, 12]: x = 5.2 is
+    # inside for both spins, x = 5.05 for spin 0 only (5^2 + 0.81 > 5.05^2)
+    o = np.array([[5.2, 0.0, 0.3], [5.05, 0.0, 0.3]])
+    d = np.array([[0.0, 0.0, -1.0], [0.0, 0.0, -1.0]])
+    for spin, second in ((0.0, True), (0.9, False)):
+        tr = kr.trace(o, d, spin, 1.0, (5.0, 12.0), 0.05, 60.0, 4000)
+        assert tr["result"][0] == kr.DISK and tr["hit"][0, 2] == 0.0
+        assert abs(tr["hit"][0, 0] - 5.2) < 0.01 and abs(tr["distance"][0] - 0.3) < 0.01
+        assert (tr["result"][1] == kr.DISK) == second, (spin, tr["result"])
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+def test_kerr_demo_builds_against_the_drop_in_headers(tmp_path):
+    exe = str(tmp_path / "kerr_demo")
+    path = os.path.abspath(lib.LIB_PATH)
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "examples", "kerr_demo.c"), path,
+                    f"-Wl,-rpath,{os.path.dirname(path)}", "-lm", "-o", exe], check=True)
+    assert os.path.exists(exe)
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+def test_host_code_on_simulated_devices_asan_ubsan(tmp_path):
+    """tests/fakehip/kerr_driver.c: every refusal with the HIP calls counted (zero), the constants
+    and tile counts a launch carries, shards and offsets, ray arrays, the host forms' round trips,
+    the statistics, bhrt_kerr_ray_init."""
+    exe = str(tmp_path / "kerr_asan")
+    wrapped = ("hipMalloc", "hipFree", "hipMemcpy", "hipMemcpyAsync", "hipSetDevice", "hipGetDevice",
+               "hipStreamSynchronize", "hipEventRecord", "hipStreamWaitEvent", "hipHostMalloc")
+    cmd = ["gcc", "-fopenmp", "-std=gnu11", "-O1", "-g", "-fsanitize=address,undefined",
+           "-fno-omit-frame-pointer", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+           "-I", "/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+           os.path.join(FAKE, "kerr_driver.c"), os.path.join(FAKE, "fake_hip.c"),
+           os.path.join(CSRC, "kerr.c"), *host_core(),
+           "-Wl," + ",".join("--wrap=" + w for w in wrapped), "-lpthread", "-lm", "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-6000:]
+    env = dict(os.environ, FAKEHIP_DEVICES="2", ASAN_OPTIONS="detect_leaks=0",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    for name in ("HIP_VISIBLE_DEVICES", "BHRT_NULL_STREAM", "BHRT_FUSE_COLOUR", "BHRT_MAX_DEVICES"):
+        env.pop(name, None)
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
+    assert "all checks passed" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, \
+        r.stderr[-4000:]
