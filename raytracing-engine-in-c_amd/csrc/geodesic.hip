@@ -1179,18 +1179,48 @@ __device__ __forceinline__ void ray_init_shared(Ray_& R, const bhrt_camera_k& cm
 // A NaN operand fails the screen's comparisons as it fails the reference's. Radii whose
 // squares times den^2 would be subnormal (below ~1e-144) are screened at the subnormals'
 // precision.
+// FAR TESTS FIRST. On a ray that never hits, the candidate point lies far outside the outer rim
+// in every iteration (C2, camera B: median |q_xy| 193 against 20), and ONE component against that
+// rim already says so: sx^2 > out_sq den^2 for every live lane of 94% of the wave-iterations
+// (tools/screen_replay.py). So the fall-through path forms only den, num, d2, sx, sxx = RN(sx sx)
+// and the outer threshold T = RN(out_sq d2): a lane with sxx > T and |den| < big is rejected at
+// once. The others (a NaN operand and |den| >= big among them: their comparisons fail) go on in
+// a rare, exec-masked block that tries RN(sy sy) > T the same way, and only a lane that
+// survives both forms sg, S and the inner threshold and takes the one-mask screen above.
+// Neither far test rejects a lane that screen passes:
+//   - RN(sy sy) >= 0, so sx sx + RN(sy sy) >= sx sx exactly; rounding is monotone, so
+//     S = fma(sx, sx, RN(sy sy)) >= RN(sx sx) = sxx, or S is NaN. Either way S <= T is false
+//     whenever sxx > T. (sxx is a product of its own, for the test alone: S keeps its FMA.)
+//   - likewise S >= RN(sy sy): the FMA rounds the exact sx sx + RN(sy sy) >= RN(sy sy) once;
+//   - with |den| < big required, the unscreened pass does not apply.
+// So the lanes that reach disk_decide are the same set, and every output the same bits
+// (profiles/farscreen/bitexact.txt; tests/test_far_screen_cpu.py checks the implication on
+// 1e5 operand sets in exact arithmetic).
 __device__ __forceinline__ bool disk_cand(const Ray_& R, double nx, double ny, double nz,
                                           const Scene& sc, double big, double& num,
                                           double& den) {
     den = (R.dx * nx + R.dy * ny) + R.dz * nz;
     num = -((R.px * nx + R.py * ny) + R.pz * nz);
     const double d2 = den * den;
-    const double sg = den * __builtin_fma(0x1p-1000, den, num);
     const double sx = __builtin_fma(R.dx, num, R.px * den);
-    const double sy = __builtin_fma(R.dy, num, R.py * den);
-    const double S = sx * sx + sy * sy;
-    return (!(sg < 0.0) & (S >= sc.disk_in_sq * d2) & (S <= sc.disk_out_sq * d2)) |
-           !(fabs(den) < big);
+    const double sxx = sx * sx;  // for the far test alone: S below keeps its own rounding
+    const double out = sc.disk_out_sq * d2;
+    bool cand = false;
+    if (__builtin_expect(!((sxx > out) & (fabs(den) < big)), 0)) {
+        // |den| < big again, of a copy the optimiser cannot see through: kept live across the
+        // branch, the mask cost the fall-through path a second compare of the same operands
+        double dn = den;
+        asm volatile("" : "+v"(dn));
+        const bool small = fabs(dn) < big;
+        const double sy = __builtin_fma(R.dy, num, R.py * den);
+        const double syy = sy * sy;
+        if (!((syy > out) & small)) {
+            const double sg = den * __builtin_fma(0x1p-1000, den, num);
+            const double S = __builtin_fma(sx, sx, syy);
+            cand = (!(sg < 0.0) & (S >= sc.disk_in_sq * d2) & (S <= out)) | !small;
+        }
+    }
+    return cand;
 }
 
 // The reference's decision for a lane that passed the screen, and its candidate point
