@@ -935,8 +935,9 @@ int  bhrt_sky_lookup(const bhrt_sky* sky, const double* dirs, int n, double* rgb
  *              a bad row sharding; BHRT_FLAG_SKY without a map bound on this device. HIP failures
  *              also return -1.
  *  Statistics. bhrt_stats counts a launch as a trace launch: rays, iterations (RK4 steps), launches.
- *  Not offered. The supersampled, adaptive, accumulator and path calls do not take this path; a
- *              caller accumulates these frames through bhrt_accum_blend_device. */
+ *  Not offered. The supersampled, adaptive and accumulator calls do not take this path; a caller
+ *              accumulates these frames through bhrt_accum_blend_device. Recorded polylines of
+ *              these rays: "Physical photon paths" below. */
 typedef struct {
     double* h_residual;
     double* lz_drift;
@@ -968,6 +969,69 @@ int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
  * a static observer. No HIP call. */
 int bhrt_kerr_ray_init(const BlackHoleParams* blackhole, const Vector3D* origin,
                        const Vector3D* direction, double state[6], double* E);
+
+/* ---- Physical photon paths: batched polylines of true Kerr geodesics ----
+ * bhrt_trace_paths records the parity path's rays, straight lines wherever spin != 0. These calls
+ * record the rays of "Physical geodesics" above instead -- how light bends: the lensing diagram,
+ * the orbits that wind round the photon sphere, the prograde / retrograde asymmetry behind the
+ * D-shaped shadow -- n rays in one launch, into bhrt_paths arrays laid out as bhrt_trace_paths'.
+ *
+ * THE RULE (tests/kerr_paths_rule.py restates it in numpy).
+ *  Full path   of ray i: q_0 .. q_{m-1} with m = steps + 1, steps being the Physical-geodesics
+ *              rule's step count for that ray, disk, config and spin. q_0 is the ray's origin as
+ *              given; q_k (1 <= k <= steps) is the position the rule keeps after step k: the step's
+ *              end point, except that the disk-hitting step contributes the hit point
+ *              (q_x, q_y, 0). So a RAY_DISK path ends on the disk, a RAY_HORIZON path on its first
+ *              point with r <= r+, a RAY_MAX_DISTANCE path on the first point past the distance, a
+ *              RAY_MAX_STEPS path on point max_integration_steps, and a RAY_ERROR from a non-finite
+ *              state on that non-finite point, stored as it is: q_{m-1} is always what hit_x/y/z
+ *              holds. A device ray whose origin has no static observer has m = 1, the origin alone,
+ *              and so has every ray with max_integration_steps == 0.
+ *  Stored points (bhrt_trace_paths_device's rule, word for word). every = e >= 1 keeps q_0, q_e,
+ *              q_2e, ... and also q_{m-1} where (m - 1) % e != 0, so the end of the ray is always
+ *              drawn. Of that list the first max_positions points are stored and count[i] is how
+ *              many were; elements of xyz / xyz32 at or beyond count[i] are NOT written. xyz32
+ *              holds (float) of xyz's doubles. Every element index into the path arrays is formed
+ *              in size_t.
+ *  Hit records. device_hits may be NULL; otherwise it and device_diag receive exactly what
+ *              bhrt_kerr_rays_device(device_rays, n, blackhole, disk, config, flags, device_hits,
+ *              device_diag, hip_stream) writes, bit for bit: that call's own k_kerr launch, queued
+ *              behind the path launch on the same stream. Colour fields and BHRT_FLAG_SKY are
+ *              allowed, so a caller can draw each path in its pixel's colour; flags is not
+ *              otherwise used. device_diag without device_hits is refused.
+ *  Which bits. The points come from the path kernel and the records from k_kerr: two compilations
+ *              of one step. q_{m-1} and hit_* agree to 1e-5 of the larger magnitude (the GPU
+ *              suite's contract), not necessarily in every bit; count[i] is the path kernel's own,
+ *              and so is the class it implies.
+ *  Determinism. No atomic touches an output: a ray's row is a pure function of its own inputs, the
+ *              same bits run to run, on any stream, whatever n is and wherever the ray stands in
+ *              the batch.
+ *  Statistics. bhrt_stats counts the path launch as a trace launch (rays n, iterations the sum of
+ *              steps, launches 1) and the hit records' launch as another.
+ *  Refusals.   -1 with bhrt_last_error set, nothing written and nothing launched, each decided
+ *              BEFORE ANY HIP CALL (the current device's query aside), the path arguments and the
+ *              hit arguments alike before the first launch: everything bhrt_kerr_rays_device
+ *              refuses for the scene (|spin| >= 1 or NaN; mass; time_step; max_integration_steps
+ *              < 0; a NaN max_ray_distance; disk radii) and for device_hits (time_dilation != NULL;
+ *              rgb not given as all three channels; BHRT_FLAG_SKY without a map bound on this
+ *              device); n <= 0; NULL rays, blackhole or config; max_positions < 1 or
+ *              > BHRT_PATHS_MAX_POSITIONS; every < 1; device_paths NULL or all three of its
+ *              pointers NULL; (long)n * max_positions > INT_MAX; device_diag without device_hits;
+ *              in the host form only, an origin without a static observer (as bhrt_kerr_rays). HIP
+ *              failures also return -1.
+ * Asynchronous on hip_stream, no host wait; NULL is ordered like the legacy default stream, as for
+ * bhrt_render_frame_device. */
+int bhrt_kerr_paths_device(const Ray* device_rays, int n, const BlackHoleParams* blackhole,
+                           const AccretionDiskParams* disk, const SimulationConfig* config,
+                           int max_positions, int every, int flags,
+                           const bhrt_paths* device_paths, const bhrt_frame_soa* device_hits,
+                           const bhrt_kerr_diag* device_diag, void* hip_stream);
+/* The same with HOST arrays on the current device; returns when they are complete. Host elements
+ * of xyz / xyz32 at or beyond count[i] keep what they held. */
+int bhrt_kerr_paths(const Ray* rays, int n, const BlackHoleParams* blackhole,
+                    const AccretionDiskParams* disk, const SimulationConfig* config,
+                    int max_positions, int every, int flags, const bhrt_paths* host_paths,
+                    const bhrt_frame_soa* host_hits, const bhrt_kerr_diag* host_diag);
 
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);

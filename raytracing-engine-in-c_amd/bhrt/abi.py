@@ -124,6 +124,10 @@ PATHS_MAX_POSITIONS = 65536  # BHRT_PATHS_MAX_POSITIONS
 # the hit fields a path launch produces (no colour or display field)
 PATH_HIT_FIELDS = ("result", "steps", "hit_x", "hit_y", "hit_z", "distance", "time_dilation",
                    "sky_x", "sky_y", "sky_z")
+# bhrt_kerr_paths: the hit fields the wrapper asks for by default (any field but time_dilation is
+# allowed, the colours included), and its default max_positions
+KERR_PATH_HIT_FIELDS = ("result", "steps", "hit_x", "hit_y", "hit_z", "distance")
+KERR_PATHS_DEFAULT_POSITIONS = 1001
 
 
 class Stats(C.Structure):

@@ -133,6 +133,14 @@ _PROTOS = {
     "bhrt_kerr_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                  _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                  _P(abi.FrameSoA), _P(abi.KerrDiag)]),
+    "bhrt_kerr_paths_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                         _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                         C.c_int, C.c_int, C.c_int, _P(abi.Paths),
+                                         _P(abi.FrameSoA), _P(abi.KerrDiag), C.c_void_p]),
+    "bhrt_kerr_paths": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                  _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
+                                  C.c_int, C.c_int, _P(abi.Paths), _P(abi.FrameSoA),
+                                  _P(abi.KerrDiag)]),
     "bhrt_kerr_ray_init": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.Vector3D), _P(abi.Vector3D),
                                      _P(C.c_double * 6), _P(C.c_double)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
@@ -649,6 +657,42 @@ def kerr_rays(rays, bh, dk, cfg, flags=0, fields=KERR_FIELDS, diag=False):
     _check(load().bhrt_kerr_rays(rays.ctypes.data, len(rays), _ptr(bh), _ptr(dk), _ptr(cfg), flags,
                                  C.byref(soa), _ptr(kd)), "bhrt_kerr_rays")
     arrays.update(extra)
+    return arrays
+
+
+def kerr_paths_device(rays_ptr, n, bh, dk, cfg, max_positions, every, flags, paths, hits=None,
+                      diag=None, stream=None):
+    """bhrt_kerr_paths_device: the recorded Kerr geodesics of n device rays (AoS Ray[n] at
+    rays_ptr) into the device arrays of `paths` (abi.Paths) and, if not None, the hit records of
+    `hits` (abi.FrameSoA) and `diag` (abi.KerrDiag), asynchronous on a hipStream_t (int handle or
+    None)."""
+    _check(load().bhrt_kerr_paths_device(C.c_void_p(rays_ptr), int(n), _ptr(bh), _ptr(dk),
+                                         _ptr(cfg), int(max_positions), int(every), int(flags),
+                                         _ptr(paths), _ptr(hits), _ptr(diag),
+                                         C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_paths_device")
+
+
+def kerr_paths(rays, bh, dk, cfg, max_positions=abi.KERR_PATHS_DEFAULT_POSITIONS, every=1, flags=0,
+               f32=False, fill=np.nan, fields=abi.KERR_PATH_HIT_FIELDS, diag=False):
+    """bhrt_kerr_paths into host numpy arrays: rays is a numpy array of abi.RAY_DTYPE. Returns a
+    dict with `xyz` [n, max_positions, 3] (float32 with f32, else float64; elements beyond a
+    ray's count keep `fill`), `count` [n], the hit fields asked for (`fields`, any of
+    KERR_FIELDS; empty: no hit records) and with diag h_residual and lz_drift."""
+    rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+    n = len(rays)
+    xyz = np.full((n, int(max_positions), 3), fill, dtype=np.float32 if f32 else np.float64)
+    count = np.zeros(n, dtype=np.int32)
+    paths = abi.Paths(xyz=None if f32 else xyz.ctypes.data, xyz32=xyz.ctypes.data if f32 else None,
+                      count=count.ctypes.data)
+    arrays, soa = abi.alloc_soa(n, fields) if fields else ({}, None)
+    extra, kd = _kerr_host_diag(n, diag)
+    _check(load().bhrt_kerr_paths(rays.ctypes.data, n, _ptr(bh), _ptr(dk), _ptr(cfg),
+                                  int(max_positions), int(every), int(flags), C.byref(paths),
+                                  _ptr(soa), _ptr(kd)), "bhrt_kerr_paths")
+    arrays.update(extra)
+    arrays["xyz"] = xyz
+    arrays["count"] = count
     return arrays
 
 

@@ -9,7 +9,7 @@
  *   batch.c        trace_ray / trace_rays_batch: the pipelined chunks
  *   dropin.c       integrate_photon_path, trace_pixel, the bh_* context API
  *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c, sky.c,
- *   kerr.c
+ *   kerr.c, kerr_paths.c
  *                  features with launchers of their own
  */
 #ifndef BHRT_HOST_H
@@ -132,8 +132,9 @@ typedef struct {
     hipEvent_t g_done, g_copied, g_wait;
     int g_wait_pending;
     unsigned long long peer_on; /* bit d: peer access to device d enabled from this device */
-    /* bhrt_render_frame_ss (supersample.c) and bhrt_trace_paths (paths.c): the device arrays of
-     * a call that returns only once its host arrays are complete */
+    /* bhrt_render_frame_ss (supersample.c), bhrt_trace_paths (paths.c), the Kerr host forms
+     * (kerr.c, kerr_paths.c): the device arrays of a call that returns only once its host arrays
+     * are complete */
     void* d_ss;
     size_t cap_ss;
 } devctx_t;
@@ -231,6 +232,25 @@ int bhrt_ss_check(const BlackHoleParams* bh, const SimulationConfig* cfg, const 
                   int W, int H, const bhrt_rows* rows, const SupersamplingParams* ss,
                   const AdaptiveSamplingParams* as, const bhrt_frame_soa* out, bhrt_ss_plan* k);
 
+/* ---- kerr.c ---- */
+/* The checks and set-up the Kerr calls share (the refusals of include/bhrt_api.h "Physical
+ * geodesics"), each 0 or -1 with the error set and no HIP call beyond the current device's query:
+ * the scene's constants; the output struct and flags; a ray array's arguments (both of the former,
+ * n and rays); whether `o` has a static observer (i: the ray's index for the message, -1 none). */
+int bhrt_kerr_scene(const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                    const SimulationConfig* cfg, bhrt_kerr_k* k);
+int bhrt_kerr_out_bad(const bhrt_frame_soa* out, int flags);
+int bhrt_kerr_rays_check(const Ray* rays, int n, const BlackHoleParams* bh,
+                         const AccretionDiskParams* dk, const SimulationConfig* cfg, int flags,
+                         const bhrt_frame_soa* out, bhrt_kerr_k* k);
+int bhrt_kerr_observer(const bhrt_kerr_k* k, const Vector3D* o, long i);
+/* bhrt_kerr_rays_device's launch for arguments that passed bhrt_kerr_rays_check (k: its
+ * constants), on `st` of context c without the NULL-stream rule */
+int bhrt_kerr_rays_on_device(devctx_t* c, hipStream_t st, const Ray* d_rays, int n,
+                             const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                             const SimulationConfig* cfg, int flags, const bhrt_frame_soa* out,
+                             const bhrt_kerr_diag* diag, const bhrt_kerr_k* k);
+
 /* ---- host_frames.c ---- */
 typedef struct {
     devctx_t* c;
@@ -238,6 +258,9 @@ typedef struct {
     long n;
 } shard_job;
 int bhrt_host_threads(void);
+/* n rows of P `elem`-byte points from a device rectangle to the caller's, count[i] points of row
+ * i and nothing beyond them (the host forms of the path calls): 0, or -1 with the error set */
+int bhrt_rows_back(void* host, const void* dev, const int32_t* count, int n, size_t P, size_t elem);
 
 /* ---- dropin.c ---- */
 struct BHContext_t { /* BHContextHandle (blackhole_api.c:26-31) */

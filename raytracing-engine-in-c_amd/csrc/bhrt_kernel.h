@@ -342,6 +342,21 @@ typedef struct {
 int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, void* stream, void* ev0,
                      void* ev1);
 
+/* Physical photon paths (kerr_paths.c; kerr.hip k_kerr_paths; the rule: include/bhrt_api.h
+ * "Physical photon paths"). The launch's bhrt_kparams carries the AoS rays, n and the control block
+ * (ctl[0]: the claim counter, ctl[1..2]: rays and RK4 steps, ctl[8..9]: the execution window; its
+ * outputs, scene and sky map are not read); this block the integration's constants -- the ones
+ * bhrt_launch_kerr gets for the same scene -- and the path outputs. */
+typedef struct {
+    bhrt_kerr_k k;        /* tiles, rows and the diag pointers are not read */
+    int max_positions, every;
+    bhrt_paths out;       /* device arrays; NULL fields skipped */
+} bhrt_kerr_paths_k;
+
+/* kerr.hip; as bhrt_launch_kerr */
+int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk, void* stream,
+                           void* ev0, void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */

@@ -21,9 +21,10 @@
 #include "bhrt_host.h"
 #include "kerr_init.h"
 
+/* The checks below are shared with kerr_paths.c through bhrt_host.h. */
 /* the scene's constants, or -1 with the error set; no HIP call */
-static int kerr_scene(const BlackHoleParams* bh, const AccretionDiskParams* dk,
-                      const SimulationConfig* cfg, bhrt_kerr_k* k) {
+int bhrt_kerr_scene(const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                    const SimulationConfig* cfg, bhrt_kerr_k* k) {
     if (!bh || !cfg) {
         bhrt_set_err("kerr: blackhole and config must not be NULL");
         return -1;
@@ -70,7 +71,7 @@ static int kerr_scene(const BlackHoleParams* bh, const AccretionDiskParams* dk,
     return 0;
 }
 
-static int kerr_out_bad(const bhrt_frame_soa* out, int flags) {
+int bhrt_kerr_out_bad(const bhrt_frame_soa* out, int flags) {
     if (!out) {
         bhrt_set_err("kerr: the output struct must not be NULL");
         return -1;
@@ -86,7 +87,7 @@ static int kerr_out_bad(const bhrt_frame_soa* out, int flags) {
     return bhrt_sky_check(flags, (flags & BHRT_FLAG_SKY) ? bhrt_current_device() : -1);
 }
 
-static int kerr_observer(const bhrt_kerr_k* k, const Vector3D* o, long i) {
+int bhrt_kerr_observer(const bhrt_kerr_k* k, const Vector3D* o, long i) {
     double f, l[3];
     if (bhrt_kerr_origin(o->x, o->y, o->z, k->a, k->a2, k->two_m, k->r_plus, &f, l)) return 0;
     if (i < 0)
@@ -103,7 +104,7 @@ static int kerr_frame_check(const BlackHoleParams* bh, const AccretionDiskParams
                             const SimulationConfig* cfg, const bhrt_camera* cam, int W, int H,
                             const bhrt_rows* rows, int flags, const bhrt_frame_soa* out,
                             bhrt_kerr_k* k, int* nrows) {
-    if (kerr_scene(bh, dk, cfg, k) || kerr_out_bad(out, flags)) return -1;
+    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags)) return -1;
     if (!cam) {
         bhrt_set_err("kerr: camera must not be NULL");
         return -1;
@@ -117,13 +118,13 @@ static int kerr_frame_check(const BlackHoleParams* bh, const AccretionDiskParams
         bhrt_set_err("kerr: invalid row sharding or frame too large (%d x %d)", W, H);
         return -1;
     }
-    return kerr_observer(k, &cam->position, -1);
+    return bhrt_kerr_observer(k, &cam->position, -1);
 }
 
-static int kerr_rays_check(const Ray* rays, int n, const BlackHoleParams* bh,
-                           const AccretionDiskParams* dk, const SimulationConfig* cfg, int flags,
-                           const bhrt_frame_soa* out, bhrt_kerr_k* k) {
-    if (kerr_scene(bh, dk, cfg, k) || kerr_out_bad(out, flags)) return -1;
+int bhrt_kerr_rays_check(const Ray* rays, int n, const BlackHoleParams* bh,
+                         const AccretionDiskParams* dk, const SimulationConfig* cfg, int flags,
+                         const bhrt_frame_soa* out, bhrt_kerr_k* k) {
+    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags)) return -1;
     if (n <= 0) {
         bhrt_set_err("kerr: n = %d rays (at least 1)", n);
         return -1;
@@ -199,9 +200,17 @@ int bhrt_kerr_rays_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
                           const AccretionDiskParams* dk, const SimulationConfig* cfg, int flags,
                           const bhrt_frame_soa* out, const bhrt_kerr_diag* diag, void* stream) {
     bhrt_kerr_k k;
-    if (kerr_rays_check(d_rays, n, bh, dk, cfg, flags, out, &k)) return -1;
+    if (bhrt_kerr_rays_check(d_rays, n, bh, dk, cfg, flags, out, &k)) return -1;
     const kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out, diag, &k};
     return bhrt_on_stream(NULL, (hipStream_t)stream, kerr_body, &a);
+}
+
+int bhrt_kerr_rays_on_device(devctx_t* c, hipStream_t st, const Ray* d_rays, int n,
+                             const BlackHoleParams* bh, const AccretionDiskParams* dk,
+                             const SimulationConfig* cfg, int flags, const bhrt_frame_soa* out,
+                             const bhrt_kerr_diag* diag, const bhrt_kerr_k* k) {
+    const kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out, diag, k};
+    return kerr_body(c, st, &a);
 }
 
 /* the host forms: `a` with host out / diag and host rays (or a camera); n rays in all */
@@ -263,9 +272,9 @@ int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* bh, const Accr
                    const SimulationConfig* cfg, int flags, const bhrt_frame_soa* out,
                    const bhrt_kerr_diag* diag) {
     bhrt_kerr_k k;
-    if (kerr_rays_check(rays, n, bh, dk, cfg, flags, out, &k)) return -1;
+    if (bhrt_kerr_rays_check(rays, n, bh, dk, cfg, flags, out, &k)) return -1;
     for (long i = 0; i < n; i++)
-        if (kerr_observer(&k, &rays[i].origin, i)) return -1;
+        if (bhrt_kerr_observer(&k, &rays[i].origin, i)) return -1;
     kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, NULL, n, flags, out, diag, &k};
     return kerr_host(&a, rays, n);
 }
@@ -278,7 +287,7 @@ int bhrt_kerr_ray_init(const BlackHoleParams* bh, const Vector3D* origin, const 
     }
     const SimulationConfig cfg = {.time_step = 1.0};
     bhrt_kerr_k k;
-    if (kerr_scene(bh, NULL, &cfg, &k) || kerr_observer(&k, origin, -1)) return -1;
+    if (bhrt_kerr_scene(bh, NULL, &cfg, &k) || bhrt_kerr_observer(&k, origin, -1)) return -1;
     const double d[3] = {direction->x, direction->y, direction->z};
     double n[3], l[3], p[3], f;
     bhrt_kerr_unit(d, n);

@@ -1,6 +1,7 @@
 // kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: the kernel
 // k_kerr and its launcher (the rule: include/bhrt_api.h "Physical geodesics"; tests/kerr_rule.py
-// restates it in numpy; the host side is kerr.c).
+// restates it in numpy; the host side is kerr.c), and k_kerr_paths, the same rays' recorded
+// polylines (below k_kerr; the host side is kerr_paths.c).
 //
 // One lane per ray, FP64, fixed-step RK4 on (x, p), no LDS. A wavefront claims 64 rays at a time
 // from the launch's claim counter -- an 8x8 pixel tile of a camera frame, so that its rays live
@@ -290,30 +291,186 @@ __global__ __launch_bounds__(64) void k_kerr(const bhrt_kparams kp, const bhrt_k
     }
 }
 
-// resident one-wave workgroups of k_kerr per device (a pure function of the device: concurrent
-// first calls store the same value)
-constexpr int kMaxDev = 64;
-std::atomic<int> g_blocks[kMaxDev];
+// The recorded polylines of a ray array (the rule: include/bhrt_api.h "Physical photon paths";
+// tests/kerr_paths_rule.py restates it; the host side is kerr_paths.c). k_kerr's ray-array branch
+// and k_kerr's step -- geom, deriv, finite6, the five tests in the rule's order, kerr_init.h's
+// initial data -- without colour, sky map or diagnostics, and with the point stores. The loop is
+// written out a second time, not shared through an inline function: with the step factored out of
+// k_kerr the compiler allocated k_kerr's registers differently, and k_kerr's
+// device code is to stay what it was.
+// Point j of the full path is the position after step j (steps == j; q_0 the origin), the hit
+// point for the step that hits the disk. A lane keeps the multiples of `every` (next_keep: the next
+// one) and, at its end, the last point if that was not one; `slot` counts what it stored, and
+// nothing is stored from max_positions on. Steps advance one at a time, so one test per step
+// decides. Direct stores: the lane writes its 24 B point (12 B of xyz32) where it is produced.
+__global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
+                                                   const bhrt_kerr_paths_k pk) {
+    const int lane = threadIdx.x;
+    const bhrt_kerr_k& kk = pk.k;
+    const size_t P = (size_t)pk.max_positions;
+    const long long every = pk.every;
+    double* const xyz = reinterpret_cast<double*>(pk.out.xyz);
+    float* const xyz32 = pk.out.xyz32;
+    const unsigned long long units = ((unsigned long long)kp.n + 63ull) / 64ull;
+    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    unsigned n_rays = 0, n_steps = 0;
+    for (;;) {
+        unsigned long long unit = 0;
+        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
+        unit = __shfl(unit, 0);
+        if (unit >= units) break;
+        const unsigned long long id = unit * 64ull + (unsigned)lane;
+        const bool live = id < (unsigned long long)kp.n;
+        const int i = live ? (int)id : 0;
+        const size_t row = (size_t)i * P;  // element index of the ray's slot 0
+        const Ray ray = kp.rays[i];
+        const double o[3] = {ray.origin.x, ray.origin.y, ray.origin.z};
+        const double dir[3] = {ray.direction.x, ray.direction.y, ray.direction.z};
+        double nv[3], l0[3], p0[3], f0, E;
+        bhrt_kerr_unit(dir, nv);
+        const bool observer =
+            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
+        bhrt_kerr_photon(f0, l0, nv, p0, &E);
+        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
+        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+        int steps = 0;
+        double dist = 0.0;
+        Geom g = geom(y[0], y[1], y[2], kk);
+        size_t slot = 0;          // points stored (or counted, without a point output)
+        long long next_keep = 0;  // the next path index that is kept
+        // the point y[0..2] is kept: into slot `slot` (the caller checked live and slot < P)
+        auto emit = [&]() {
+            const size_t e = (row + slot) * 3;
+            if (xyz) {
+                xyz[e] = y[0];
+                xyz[e + 1] = y[1];
+                xyz[e + 2] = y[2];
+            }
+            if (xyz32) {
+                xyz32[e] = (float)y[0];
+                xyz32[e + 1] = (float)y[1];
+                xyz32[e + 2] = (float)y[2];
+            }
+            slot++;
+            next_keep += every;
+        };
+        if (live) emit();  // q_0, the origin as given; max_positions >= 1
+        bool run = live && res < 0;
+        while (__ballot(run) != 0ull) {
+            if (run) {
+                const double h = kk.dt * fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
+                const double hh = 0.5 * h;
+                double k1[6], k2[6], k3[6], k4[6], s[6];
+                deriv(g, y[0], y[1], y[2], y[3], y[4], y[5], E, kk, k1);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k1[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k2[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + h * k3[c];
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
+                const double h6 = h / 6.0;
+                double yn[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++)
+                    yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
+                steps++;
+                const double cx = yn[0] - y[0], cy = yn[1] - y[1], cz = yn[2] - y[2];
+                const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
+                const Geom gn = geom(yn[0], yn[1], yn[2], kk);
+                const double zo = y[2], zn = yn[2];
+                if (!finite6(yn)) {  // 1. a non-finite state
+                    res = RAY_ERROR;
+                } else {
+                    if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
+                        const double t = zo / (zo - zn);  // 2. the disk
+                        const double qx = y[0] + t * cx, qy = y[1] + t * cy;
+                        const double s2 = qx * qx + qy * qy;
+                        if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+                            res = RAY_DISK;
+                            yn[0] = qx;
+                            yn[1] = qy;
+                            yn[2] = 0.0;
+                            dist += t * seg;
+                        }
+                    }
+                    if (res < 0) {
+                        if (gn.r <= kk.r_plus) {  // 3. the horizon
+                            res = RAY_HORIZON;
+                        } else {
+                            dist += seg;  // 4. the distance
+                            if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
+                            else if (steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 5.
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 6; c++) y[c] = yn[c];
+                g = gn;
+                run = res < 0;
+                // q_steps: a kept index, or the end of the ray unless it was just kept (next_keep -
+                // every: the last kept index; a truncated ray stores no more)
+                if (slot < P && (next_keep == (long long)steps ||
+                                 (!run && next_keep - every != (long long)steps)))
+                    emit();
+            }
+        }
+        if (!live) continue;
+        n_rays++;
+        n_steps += (unsigned)steps;
+        if (pk.out.count) pk.out.count[i] = (int)slot;
+    }
+    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
+    if (lane == 0) {
+        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
+        if (s0) atomicAdd(kp.ctl + 1, s0);
+        if (s1) atomicAdd(kp.ctl + 2, s1);
+    }
+}
 
-int resident_blocks() {
+// resident one-wave workgroups of a kernel per device (a pure function of the device: concurrent
+// first calls store the same value); which: 0 k_kerr, 1 k_kerr_paths
+constexpr int kMaxDev = 64;
+std::atomic<int> g_blocks[2][kMaxDev];
+
+int resident_blocks(int which = 0) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    int blocks = g_blocks[dev].load(std::memory_order_relaxed);
+    int blocks = g_blocks[which][dev].load(std::memory_order_relaxed);
     if (blocks == 0) {
         int cus = 0, per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
             cus <= 0)
             cus = 256;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&k_kerr), 64, 0);
+            &per_cu,
+            which ? reinterpret_cast<const void*>(&k_kerr_paths)
+                  : reinterpret_cast<const void*>(&k_kerr),
+            64, 0);
         if (per_cu <= 0) per_cu = 1;
         blocks = cus * per_cu;
-        g_blocks[dev].store(blocks, std::memory_order_relaxed);
+        g_blocks[which][dev].store(blocks, std::memory_order_relaxed);
     }
     return blocks;
 }
 
 }  // namespace
+
+extern "C" int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk,
+                                      void* stream, void* ev0, void* ev1) {
+    if (kp->n <= 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
+    const long units = ((long)kp->n + 63) / 64;
+    long blocks = resident_blocks(1);
+    if (blocks > units) blocks = units;
+    if (e0) (void)hipEventRecord(e0, st);
+    k_kerr_paths<<<(unsigned)blocks, 64, 0, st>>>(*kp, *pk);
+    if (e1) (void)hipEventRecord(e1, st);
+    return (int)hipGetLastError();
+}
 
 extern "C" int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, void* stream,
                                 void* ev0, void* ev1) {

@@ -136,52 +136,6 @@ int bhrt_trace_paths_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
     return bhrt_on_stream(c, (hipStream_t)stream, paths_body, &a);
 }
 
-/* A copy call's fixed cost, as the bytes a transfer moves meanwhile (about 10 us at the rate of
- * a copy into pageable memory); BHRT_PATHS_COPY_CALL_BYTES overrides it (tests, A/B). */
-static size_t copy_call_bytes(void) {
-    const char* e = getenv("BHRT_PATHS_COPY_CALL_BYTES");
-    return e ? (size_t)strtoull(e, NULL, 10) : (size_t)131072;
-}
-
-/* Rows of `elem`-byte points back to the caller, count[i] points of ray i and nothing beyond
- * them. Decided by total bytes: the whole rectangle moves n * P * elem bytes in one call (into a
- * host staging block, the stored points then copied row by row: the caller's tails must keep what
- * they hold); the ragged form moves only sum(count) * elem bytes but in one call per ray, each
- * costing copy_call_bytes() more. The rectangle is taken when it is no more than the ragged total.
- * A batch whose every row is full is its rectangle: one copy straight into the caller's array. */
-static int rows_back(void* host, const void* dev, const int32_t* count, int n, size_t P,
-                     size_t elem) {
-    size_t total = 0;
-    for (int i = 0; i < n; i++) total += (size_t)count[i];
-    const size_t rect = (size_t)n * P * elem;
-    if (total == (size_t)n * P) {
-        HIP_TRY(hipMemcpy(host, dev, rect, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    if (rect <= total * elem + (size_t)n * copy_call_bytes()) {
-        char* stage = (char*)malloc(rect);
-        if (stage) {
-            if (hipMemcpy(stage, dev, rect, hipMemcpyDeviceToHost) != hipSuccess) {
-                free(stage);
-                bhrt_set_err("paths: readback failed: %s", hipGetErrorString(hipGetLastError()));
-                return -1;
-            }
-            for (int i = 0; i < n; i++)
-                memcpy((char*)host + (size_t)i * P * elem, stage + (size_t)i * P * elem,
-                       (size_t)count[i] * elem);
-            free(stage);
-            return 0;
-        }
-        /* (no memory for the staging block: the ragged form needs none) */
-    }
-    for (int i = 0; i < n; i++)
-        if (count[i] > 0)
-            HIP_TRY(hipMemcpy((char*)host + (size_t)i * P * elem,
-                              (const char*)dev + (size_t)i * P * elem, (size_t)count[i] * elem,
-                              hipMemcpyDeviceToHost));
-    return 0;
-}
-
 int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
                      const AccretionDiskParams* dk, const SimulationConfig* cfg,
                      IntegrationMethod method, int max_positions, int every,
@@ -237,9 +191,9 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* bh,
         rc = -1;
     }
     if (rc == 0 && paths->xyz)
-        rc = rows_back(paths->xyz, dev.xyz, count, n, P, sizeof(Vector3D));
+        rc = bhrt_rows_back(paths->xyz, dev.xyz, count, n, P, sizeof(Vector3D));
     if (rc == 0 && paths->xyz32)
-        rc = rows_back(paths->xyz32, dev.xyz32, count, n, P, 3 * sizeof(float));
+        rc = bhrt_rows_back(paths->xyz32, dev.xyz32, count, n, P, 3 * sizeof(float));
     free(own_count);
     if (rc) return -1;
     for (int i = 0; hits && i < BHRT_NFIELDS; i++)
