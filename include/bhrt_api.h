@@ -629,25 +629,25 @@ int bhrt_trace_paths(const Ray* rays, int n, const BlackHoleParams* blackhole,
                      const bhrt_paths* host_paths, const bhrt_frame_soa* host_hits);
 
 /* Diagnostic: both forms of the trace kernel's RKF45 accept test (the division-free fast
- * form and the reference's literal quotient, geodesic.hip rkf45_accept) on n cases of DEVICE
+ * form and the reference's literal quotient, bhrt_trace_core.h rkf45_accept) on n cases of DEVICE
  * arrays err[6n], scale[6n], tol[n]; d_out[2i] / d_out[2i+1] = the two decisions. Returns 0
  * or a hipError_t value; asynchronous on hip_stream. */
 int bhrt_check_rkf45_accept(const double* err, const double* scale, const double* tol, int n,
                             int* out, void* hip_stream);
 
-/* Diagnostic: the trace loop's disk decision (geodesic.hip disk_hit) on n cases of DEVICE arrays
+/* Diagnostic: the trace loop's disk decision (bhrt_trace_core.h disk_hit) on n cases of DEVICE arrays
  * p[3n] (the point), d[3n] (the direction) and nrm[3n] (the plane "normal": the previous path
  * point), against the squared-radius thresholds in_sq <= s <= out_sq; d_out[i] = 1 for a hit.
  * Returns 0 or a hipError_t value; asynchronous on hip_stream. */
 int bhrt_check_disk_hit(const double* p, const double* d, const double* nrm, int n, double in_sq,
                         double out_sq, int* out, void* hip_stream);
 
-/* Diagnostic: the square root the trace loop takes for a segment's length (geodesic.hip
+/* Diagnostic: the square root the trace loop takes for a segment's length (bhrt_trace_core.h
  * seg_len) of n DEVICE arguments x; d_out[i] = the root. Returns 0 or a hipError_t value;
  * asynchronous on hip_stream. */
 int bhrt_check_seg_len(const double* x, int n, double* out, void* hip_stream);
 
-/* Diagnostic: the reciprocal two RK4 a = 0 stages share (geodesic.hip pair_rcp) on n cases of a
+/* Diagnostic: the reciprocal two RK4 a = 0 stages share (bhrt_trace_core.h pair_rcp) on n cases of a
  * DEVICE array in[4n] = (rc_a, st_a, rc_b, st_b), the stages' clamped r and sin theta;
  * d_out[5i..5i+3] = 1 / rc_a, 1 / st_a, 1 / rc_b, 1 / st_b as the stages form them, d_out[5i+4]
  * = 1.0 where the pair's range test passes (0.0: both stages take the literal form, not these).
@@ -655,7 +655,7 @@ int bhrt_check_seg_len(const double* x, int n, double* out, void* hip_stream);
  * asynchronous on hip_stream. */
 int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hip_stream);
 
-/* Diagnostic: a chained angle shift of the RK4 a = 0 iteration (geodesic.hip shift_chain) on n
+/* Diagnostic: a chained angle shift of the RK4 a = 0 iteration (bhrt_trace_core.h shift_chain) on n
  * cases of a DEVICE array in[4n] = (a, s0, c0, x): sin and cos of x from s0 = sin a, c0 = cos a.
  * site 0: stage 3 from stage 2's angle (two coefficients, |x - a| <= 1/64); site 1: the advance
  * of state[1] from stage 4's angle (one coefficient, |x - a| <= 2^-10). d_out[5i..5i+1] = sin x,
@@ -666,7 +666,7 @@ int bhrt_check_pair_rcp(const double* in, int n, int huge, double* out, void* hi
 int bhrt_check_shift_chain(const double* in, int n, int site, double* out, void* hip_stream);
 
 /* Diagnostic: a guard of the trace loop that is decided from the high words of its f64 operands
- * (geodesic.hip all_below_2), beside the exact test it filters for, on n cases of DEVICE
+ * (bhrt_trace_core.h all_below_2), beside the exact test it filters for, on n cases of DEVICE
  * arrays. kind 0 (the one guard built): the plain-value test of a stage's three accelerations,
  * a[3n] (b is not read and may be NULL). d_out[2i] = 1 where the high-word filter keeps the case
  * on the straight-line path, d_out[2i+1] = 1 where the exact test (every |a| <= 10) passes; the

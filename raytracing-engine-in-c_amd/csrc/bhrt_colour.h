@@ -1,6 +1,7 @@
 // bhrt_colour.h -- the frame colour contract and the sky-map lookup as device functions, shared by
-// the kernels of geodesic.hip and kerr.hip. Included inside the including file's unnamed namespace,
-// after `using Scene = bhrt_scene_k;`. The text below is geodesic.hip's own, moved here unchanged:
+// the kernels of geodesic.hip, paths.hip, frames.hip and checks.hip (through bhrt_trace_core.h,
+// which includes this) and of kerr.hip. Included inside the including file's unnamed namespace,
+// after `using Scene = bhrt_scene_k;`. The text below was geodesic.hip's own, moved here unchanged:
 // every function is the same IEEE operation sequence wherever it is inlined.
 
 __device__ __forceinline__ double clampd(double v, double lo, double hi) {

@@ -1,7 +1,8 @@
 /*
  * bhrt_kernel.h -- launch parameters shared by the C host layer (bhrt_host.h) and the HIP
- * kernels (geodesic.hip). Plain C, passed by value as the kernel argument block, so every
- * field is wave-uniform and read through the scalar unit.
+ * kernels (geodesic.hip, paths.hip, frames.hip, kerr.hip, particles.hip). Plain C, passed by
+ * value as the kernel argument block, so every field is wave-uniform and read through the scalar
+ * unit.
  *
  * Everything that is the same for all rays of a launch is computed ONCE on the host with
  * the same IEEE operations the reference performs inline (so identical rounding):
@@ -46,13 +47,16 @@ typedef struct {
     int flags;   /* BHRT_FLAG_* */
     int spin0;   /* blackhole->spin == 0.0 */
     int far_bounded; /* a state within 2^40 stays below 2^400 over max_steps steps, far-field
-                        branch included (scene.c far_bounded; geodesic.hip repair_at_refill) */
+                        branch included (scene.c far_bounded; bhrt_trace_core.h
+                        repair_at_refill) */
     double rot_vmax; /* zero-acceleration paths: a ray with |state[5]| below this turns state[2]
-                        by less than pi/4 per step for every step size (geodesic.hip
+                        by less than pi/4 per step for every step size (bhrt_trace_core.h
                         rotation_trig); a ray at or above it is re-traced by the redo pass */
     int accept_all;  /* RKF45 with 2^-30 <= tol <= 2^300 and finite step sizes: no attempt on the
-                        zero-acceleration paths can be rejected (geodesic.hip rkf45_attempt ACC) */
-    double m_4;      /* M / 4: the a = 0 stage forms -M / r^2 from -2 / r (geodesic.hip rhs) */
+                        zero-acceleration paths can be rejected (bhrt_trace_core.h rkf45_attempt
+                        ACC) */
+    double m_4;      /* M / 4: the a = 0 stage forms -M / r^2 from -2 / r (bhrt_trace_core.h
+                        rhs) */
 } bhrt_scene_k;
 
 typedef struct {
@@ -84,7 +88,7 @@ typedef struct {
 
 /* The bound sky map of a launch with BHRT_FLAG_SKY (the rule: include/bhrt_api.h "Sky maps"); all
  * zero otherwise. The record is the calling thread's (scene.c bhrt_sky_bind), copied here by
- * bhrt_fill_scene; the kernels read it at a ray's exit only (geodesic.hip sky_lookup). */
+ * bhrt_fill_scene; the kernels read it at a ray's exit only (bhrt_colour.h sky_lookup). */
 typedef struct {
     const void* tex;      /* device [h][w] texels, 16 bytes each: r, g, b as float and a pad, so
                              one tap is one aligned load; NULL: no sky */
@@ -100,7 +104,7 @@ typedef struct {
  * frame's persistent workgroups held every wave slot, so a C2 frame's colour landed ~1 frame
  * late (k_colour dispatches averaged 5.5 ms), and fusing costs nothing (C2 284.5 vs 284.6
  * Mrays/s same box, profiles/r06/ab_fused_colour.txt; C5 +16%, C1 +9%). Scenes without a disk
- * get the sky / horizon colour alone (geodesic.hip colour_sky). BHRT_FUSE_COLOUR=0 at run time
+ * get the sky / horizon colour alone (bhrt_colour.h colour_sky). BHRT_FUSE_COLOUR=0 at run time
  * takes the separate pass (A/B, and the tests' reference path). */
 
 typedef struct {
@@ -152,7 +156,7 @@ typedef struct {
                              field keeps its place in the kernel argument segment */
 } bhrt_kparams;
 
-/* Supersampled camera frames (supersample.c; geodesic.hip k_ss_rays, k_ss_resolve): two
+/* Supersampled camera frames (supersample.c; frames.hip k_ss_rays, k_ss_resolve): two
  * elementwise kernels around ONE shared-origin trace of n * samples rays. The sample rays are
  * sample-major -- ray s * n + p is shard pixel p (camera_dir's index) at sample s -- so sample
  * plane s is exactly the frame at offset s. k_ss_rays is launched once per sample, the sample's
@@ -174,11 +178,11 @@ typedef struct {
     bhrt_frame_soa out;         /* result, rgb_r/g/b, rgba32f, rgba8; NULL fields skipped */
 } bhrt_ss_resolve_k;
 
-/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+/* frames.hip; asynchronous on `stream`; return 0 or a hipError_t value */
 int bhrt_launch_ss_rays(const bhrt_ss_rays_k* k, void* stream);
 int bhrt_launch_ss_resolve(const bhrt_ss_resolve_k* k, void* stream);
 
-/* Adaptive supersampled frames (adaptive.c; geodesic.hip k_ad_rays, k_ad_edges, k_ad_resolve;
+/* Adaptive supersampled frames (adaptive.c; frames.hip k_ad_rays, k_ad_edges, k_ad_resolve;
  * the rule is stated in bhrt_api.h). Rays are addressed by IMAGE pixel: the camera block is the
  * whole image's (rows = {0, 0, 1}), and the shard enters through two row tables.
  *   ext rows   the image rows the base pass traces, ascending: the shard's own rows and its
@@ -225,12 +229,12 @@ typedef struct {
     int32_t* samples;     /* S(p), or NULL                                                   */
 } bhrt_ad_resolve_k;
 
-/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+/* frames.hip; asynchronous on `stream`; return 0 or a hipError_t value */
 int bhrt_launch_ad_rays(const bhrt_ad_rays_k* k, void* stream);
 int bhrt_launch_ad_edges(const bhrt_ad_edges_k* k, void* stream);
 int bhrt_launch_ad_resolve(const bhrt_ad_resolve_k* k, void* stream);
 
-/* Temporal accumulation (temporal.c; geodesic.hip k_ta_blend, k_ta_edges; the rule is stated in
+/* Temporal accumulation (temporal.c; frames.hip k_ta_blend, k_ta_edges; the rule is stated in
  * bhrt_api.h). Two elementwise kernels behind the unchanged camera-frame launch: the blend with
  * the display conversion, then -- whole images only -- the edge stencil on the UPDATED acc, a
  * launch of its own because the blend updates acc in place (a lane that recomputed its
@@ -255,11 +259,11 @@ typedef struct {
     float* out;           /* [n] copy of the new edge, or NULL                                */
 } bhrt_ta_edges_k;
 
-/* geodesic.hip; asynchronous on `stream`; return 0 or a hipError_t value */
+/* frames.hip; asynchronous on `stream`; return 0 or a hipError_t value */
 int bhrt_launch_ta_blend(const bhrt_ta_blend_k* k, void* stream);
 int bhrt_launch_ta_edges(const bhrt_ta_edges_k* k, void* stream);
 
-/* Batched photon paths (paths.c; geodesic.hip k_paths): the launch's bhrt_kparams carries the
+/* Batched photon paths (paths.c; paths.hip k_paths): the launch's bhrt_kparams carries the
  * scene, the AoS rays, n and the control block (ctl[0]: the claim counter, ctl[1..5]: the
  * statistics, as k_trace's; its hit outputs are not used); this block the path outputs. */
 #ifndef BHRT_PATHS_STAGED /* the default store form: 1 staged through LDS, 0 direct (the faster
@@ -274,7 +278,7 @@ typedef struct {
     bhrt_paths out;       /* device arrays; NULL fields skipped */
 } bhrt_paths_k;
 
-/* geodesic.hip; asynchronous on `stream`, ev0/ev1 (hipEvent_t, may be NULL) recorded around the
+/* paths.hip; asynchronous on `stream`, ev0/ev1 (hipEvent_t, may be NULL) recorded around the
  * kernel; returns 0 or a hipError_t value */
 int bhrt_launch_paths(const bhrt_kparams* kp, const bhrt_paths_k* pk, void* stream, void* ev0,
                       void* ev1);
@@ -312,7 +316,7 @@ int bhrt_launch_particles_scatter(const Particle* d_particles, int count, const 
                                   int max_count, const bhrt_particle_data* out, void* stream,
                                   void* ev0, void* ev1);
 
-/* Sky lookups by themselves (sky.c; geodesic.hip k_sky_lookup): rgb[i] = the lookup of dirs[i],
+/* Sky lookups by themselves (sky.c; frames.hip k_sky_lookup): rgb[i] = the lookup of dirs[i],
  * n > 0 directions, asynchronous on `stream`; 0 or a hipError_t value */
 int bhrt_launch_sky(const bhrt_sky_k* sky, const double* d_dirs, int n, double* d_rgb,
                     void* stream);
@@ -363,6 +367,7 @@ int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk, 
 int bhrt_launch_trace(const bhrt_kparams* kp, void* stream, void* ev0, void* ev1);
 /* 1 if bhrt_launch_trace runs kp's RKF45 attempts without the accept test (bhrt_stats) */
 int bhrt_trace_untested(const bhrt_kparams* kp);
+/* paths.hip (k_path); return 0 or a hipError_t value */
 int bhrt_launch_path(const bhrt_kparams* kp, const double* origin4, const double* dir3,
                      Vector3D* d_path, int max_positions, int* d_num, int num_positions_in,
                      void* stream);

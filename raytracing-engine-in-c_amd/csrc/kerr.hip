@@ -16,9 +16,8 @@
 // claim counter and the statistics are the only atomics.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "bhrt_kernel.h"
+#include "bhrt_launch.h"
 #include "kerr_init.h"
 
 namespace {
@@ -430,32 +429,6 @@ __global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
     }
 }
 
-// resident one-wave workgroups of a kernel per device (a pure function of the device: concurrent
-// first calls store the same value); which: 0 k_kerr, 1 k_kerr_paths
-constexpr int kMaxDev = 64;
-std::atomic<int> g_blocks[2][kMaxDev];
-
-int resident_blocks(int which = 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    int blocks = g_blocks[which][dev].load(std::memory_order_relaxed);
-    if (blocks == 0) {
-        int cus = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus <= 0)
-            cus = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu,
-            which ? reinterpret_cast<const void*>(&k_kerr_paths)
-                  : reinterpret_cast<const void*>(&k_kerr),
-            64, 0);
-        if (per_cu <= 0) per_cu = 1;
-        blocks = cus * per_cu;
-        g_blocks[which][dev].store(blocks, std::memory_order_relaxed);
-    }
-    return blocks;
-}
-
 }  // namespace
 
 extern "C" int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk,
@@ -464,7 +437,7 @@ extern "C" int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_pa
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
     const long units = ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks(1);
+    long blocks = resident_blocks_cached<&k_kerr_paths>(64);  // one-wave workgroups (bhrt_launch.h)
     if (blocks > units) blocks = units;
     if (e0) (void)hipEventRecord(e0, st);
     k_kerr_paths<<<(unsigned)blocks, 64, 0, st>>>(*kp, *pk);
@@ -478,7 +451,7 @@ extern "C" int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, v
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
     const long units = kp->src == BHRT_SRC_CAMERA ? (long)kk->ntiles : ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks();
+    long blocks = resident_blocks_cached<&k_kerr>(64);
     if (blocks > units) blocks = units;
     if (e0) (void)hipEventRecord(e0, st);
     k_kerr<<<(unsigned)blocks, 64, 0, st>>>(*kp, *kk);

@@ -1,6 +1,6 @@
 /*
  * paths.c -- batched photon paths: the recorded polylines of n rays in one launch
- * (bhrt_api.h bhrt_trace_paths_device / bhrt_trace_paths; geodesic.hip k_paths).
+ * (bhrt_api.h bhrt_trace_paths_device / bhrt_trace_paths; paths.hip k_paths).
  *
  * The device form is one launch of k_paths on the caller's stream, timed and counted like a
  * trace launch: it takes a control block of the context's ring through bhrt_ctx_launch_fn (the

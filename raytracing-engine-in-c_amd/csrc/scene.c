@@ -104,7 +104,7 @@ static double sqrt_upper_bound(double outer) {
 }
 
 /* Whether every state the trace loop can reach from an initial state within 2^40 stays below
- * 2^400 for max_steps steps with the far-field branch taking part (geodesic.hip
+ * 2^400 for max_steps steps with the far-field branch taking part (bhrt_trace_core.h
  * repair_at_refill: the far-field instantiations then run the state recovery once per ray and
  * the division-free RKF45 accept test). Stage accelerations are clamped to 10, zero, or -- in
  * the far-field branch, only where y0 > 15 rs -- y5 * 2M / y0^2 with a factor below
@@ -233,7 +233,7 @@ int bhrt_fill_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const Accretion
     s->h_5 = fmin(dt * 0.01, 0.1);
     s->h_15 = fmin(dt * 0.1, 0.1);
     s->h_far = fmin(dt, 0.1);
-    /* the r interval each step size holds on (geodesic.hip ray_iterate caches the size and its
+    /* the r interval each step size holds on (bhrt_trace_core.h ray_iterate caches the size and its
      * interval per ray): the chain picks h_2_5 for r < t3, else h_5 for r < t2, else h_15 for
      * r < t1, else h_far -- for any order of the thresholds */
     {
@@ -262,7 +262,7 @@ int bhrt_fill_scene(bhrt_kparams* kp, const BlackHoleParams* bh, const Accretion
     s->spin0 = bh->spin == 0.0;
     s->far_bounded = far_bounded(s);
     /* on the zero-acceleration paths an attempt's error is rounding alone, < 6e-15 of its scale
-     * (proof at geodesic.hip rkf45_attempt): every attempt is accepted for tol >= 2^-30.
+     * (proof at bhrt_trace_core.h rkf45_attempt): every attempt is accepted for tol >= 2^-30.
      * BHRT_ACCEPT_ALL=0 keeps the test (A/B) */
     s->accept_all = method == INTEGRATOR_RKF45 && s->tol >= 0x1p-30 && s->tol <= 0x1p300 &&
                     isfinite(s->h_2_5) && isfinite(s->h_5) && isfinite(s->h_15) &&

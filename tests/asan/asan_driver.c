@@ -2,8 +2,9 @@
  *
  * Built by tests/test_sanitizers.py with -fsanitize=address,undefined from: the oracle
  * (oracle/oracle.c), libbhrt's host C (the Makefile's HOST_CORE files) and the
- * stubs below for the three device launchers (geodesic.hip / particles.hip are device code,
- * not instrumented; without a GPU every device entry point must fail cleanly anyway). */
+ * stubs below for the three device launchers (geodesic.hip, paths.hip and particles.hip are
+ * device code, not instrumented; without a GPU every device entry point must fail cleanly
+ * anyway). */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -1,4 +1,4 @@
-"""The trace loop's disk screen (geodesic.hip disk_cand) as a rule on float64 operands, in
+"""The trace loop's disk screen (bhrt_trace_core.h disk_cand) as a rule on float64 operands, in
 exact arithmetic: every product and FMA is the correctly rounded value of its exact result,
 float(Fraction) -- here through integers, which is the same number (test_far_screen_cpu.py checks
 the two against each other).

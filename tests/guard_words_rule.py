@@ -1,4 +1,4 @@
-"""The high-word filter of the trace loop's plain-value test (geodesic.hip all_below_2), restated
+"""The high-word filter of the trace loop's plain-value test (bhrt_trace_core.h all_below_2), restated
 in numpy for the CPU and GPU tests, and the operands both run it on.
 
 The filter ORs the high 32 bits of three doubles and reads the result as a float: its magnitude

@@ -22,3 +22,8 @@ def host_core():
 def host_feature():
     """HOST_FEATURE: the files that name launchers of their own (absolute paths)."""
     return _listed("print-host-feature")
+
+
+def hip_sources():
+    """HIP_SRCS: the device units hipcc compiles (absolute paths)."""
+    return _listed("print-hip")

@@ -1,4 +1,4 @@
-"""The far tests of the disk screen (geodesic.hip disk_cand) never reject a lane the one-mask screen
+"""The far tests of the disk screen (bhrt_trace_core.h disk_cand) never reject a lane the one-mask screen
 passes: the implication "far test true => screen false", checked by brute force on the exact rule
 of tests/far_screen_rule.py (correctly rounded products and FMAs), and the frames of
 tests/test_gpu_far_screen.py checked on the CPU, compiled reference against the oracle port.

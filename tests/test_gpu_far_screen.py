@@ -1,4 +1,4 @@
-"""The disk screen with its far tests first (geodesic.hip disk_cand): a segment whose candidate
+"""The disk screen with its far tests first (bhrt_trace_core.h disk_cand): a segment whose candidate
 point lies beyond the outer rim in x alone, or in y alone, is rejected before the rest of the
 screen is formed. The decision must stay the reference's:
 

@@ -1,4 +1,4 @@
-"""The trace loop's high-word guard (geodesic.hip all_below_2): the plain-value
+"""The trace loop's high-word guard (bhrt_trace_core.h all_below_2): the plain-value
 test of a stage's three accelerations is filtered by one OR of their high words and one 32-bit
 compare, and a lane the filter holds back takes the exact test (every |d| <= 10) in the rare
 block before anything else.

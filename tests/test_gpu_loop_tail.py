@@ -1,4 +1,4 @@
-"""The tail of the trace loop's iteration (geodesic.hip): the disk decision without a quotient
+"""The tail of the trace loop's iteration (bhrt_trace_core.h): the disk decision without a quotient
 (disk_cand / disk_decide) and the one-correction square root of the segment length (seg_len).
 
   * frames whose disk rims cross many pixels, every ray against the oracle;

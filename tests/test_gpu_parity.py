@@ -543,7 +543,7 @@ def test_large_argument_rays_take_the_redo_path(bhrt_lib, oracle):
 
 @pytest.mark.parametrize("method", [abi.INTEGRATOR_RK4, abi.INTEGRATOR_RKF45])
 def test_unbounded_far_field_launch_takes_the_redo_path(bhrt_lib, oracle, method):
-    """geodesic.hip repair_at_refill: the far-field instantiations drop the per-iteration state
+    """bhrt_trace_core.h repair_at_refill: the far-field instantiations drop the per-iteration state
     recovery (and RKF45's literal accept quotient) only where scene.c far_bounded proves that
     no state can overflow. A tiny black hole (M = 1e-3: the far-field factor 2M / (15 rs)^2 is
     2.2, so h S C > 1/2) is not provable: every ray is handed to the HUGE redo pass, whose
@@ -792,7 +792,7 @@ def test_null_stream_trace_rays_device_orders_after_default_stream(bhrt_lib, ora
 
 @pytest.mark.parametrize("tol", [1e-8, 2.0**-30, 1e-12])
 def test_accept_all_attempts_equal_the_tested_ones(bhrt_lib, oracle, monkeypatch, tol):
-    """rkf45_attempt ACC (geodesic.hip): on the zero-acceleration RKF45 paths an attempt's error
+    """rkf45_attempt ACC (bhrt_trace_core.h): on the zero-acceleration RKF45 paths an attempt's error
     is rounding alone, so for tol >= 2^-30 the host lets every attempt through without the
     accept test. The frame must be bit-identical to the one that runs the test
     (BHRT_ACCEPT_ALL=0) and equal the oracle; below 2^-30 (1e-12) the test runs either way.
@@ -1044,7 +1044,7 @@ def test_torch_after_libbhrt_in_a_fresh_process():
 
 
 def test_rkf45_accept_band(bhrt_lib):
-    """The trace kernel's RKF45 accept test (geodesic.hip rkf45_accept): the
+    """The trace kernel's RKF45 accept test (bhrt_trace_core.h rkf45_accept): the
     division-free fast form -- q = err * rcp(scale) decides outside a +-2^-40 band around
     tol, the IEEE quotient inside it -- must make the reference's decision
     RN(max_i RN(err_i / scale_i) / tol) <= 1 (math_util.c:376-405) exactly, including

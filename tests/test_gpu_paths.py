@@ -1,4 +1,4 @@
-"""Batched photon paths on the GPU (bhrt_trace_paths_device / bhrt_trace_paths, geodesic.hip
+"""Batched photon paths on the GPU (bhrt_trace_paths_device / bhrt_trace_paths, paths.hip
 k_paths) against the compiled reference's fixture (tests/golden/path_batch.npz) and, for shapes
 beyond it, the oracle's orc_integrate_photon_path / orc_trace_ray_method, both through the rule
 functions of tests/test_paths_cpu.py.

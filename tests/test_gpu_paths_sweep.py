@@ -1,4 +1,4 @@
-"""The path kernels (geodesic.hip k_paths / k_path) on the scene sweep (tests/sweep_scenes.py):
+"""The path kernels (paths.hip k_paths / k_path) on the scene sweep (tests/sweep_scenes.py):
 the 181 edge rays of rays_rk4_disk.npz in one bhrt_trace_paths_device call per scene -- two full
 waves and a ragged one of 53 lanes, path lengths from 2 points to the step budget inside every
 wave -- with the scene's disk and with disk = NULL, against the oracle's paths

@@ -1,4 +1,4 @@
-"""The RK4 a = 0 iteration on two reciprocals (stage pairs (1,2) and (3,4), geodesic.hip rk4_step)
+"""The RK4 a = 0 iteration on two reciprocals (stage pairs (1,2) and (3,4), bhrt_trace_core.h rk4_step)
 and its two chained angle shifts (shift_chain): stage 3's theta from stage 2's, and the advance
 of state[1] from stage 4's.
 

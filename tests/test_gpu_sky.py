@@ -218,7 +218,7 @@ def test_frames_against_the_reference(bhrt_lib, smooth, k):
 def test_disk_and_horizon_pixels_keep_the_flagless_bits(bhrt_lib, smooth, k):
     """Disk and horizon pixels of the frame with the flag equal the flagless frame bit for bit:
     the sky launch runs its own instantiation of the trace kernel, and its iterations must compile
-    as the plain one's (the lookup is kept out of line for that: geodesic.hip colour_of_sky)."""
+    as the plain one's (the lookup is kept out of line for that: bhrt_colour.h colour_of_sky)."""
     result, _, name = _fixture(k)[6:]
     got = _frame(bhrt_lib, k)
     plain = _frame(bhrt_lib, k, flags_extra=0)

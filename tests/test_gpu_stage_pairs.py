@@ -1,4 +1,4 @@
-"""The reciprocal that RK4's a = 0 stages 2 and 3 share (geodesic.hip pair_rcp, rk4_step) and
+"""The reciprocal that RK4's a = 0 stages 2 and 3 share (bhrt_trace_core.h pair_rcp, rk4_step) and
 the exact trims beside it (the -2 folded into the reciprocal, the trip's exits as masks).
 
   * the shared reciprocal on crafted operands (bhrt_check_pair_rcp) against exact quotients;

@@ -1,4 +1,4 @@
-"""CPU check of the rule behind the trace loop's high-word guard (geodesic.hip all_below_2,
+"""CPU check of the rule behind the trace loop's high-word guard (bhrt_trace_core.h all_below_2,
 restated in guard_words_rule.py): on fixed special operands and seeded random ones the filter
 says "straight-line path" exactly for the triples whose members are all finite and below 2 in
 magnitude, so it never passes a triple the exact test (every |x| <= 10) fails."""

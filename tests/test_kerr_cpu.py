@@ -15,7 +15,7 @@ import pytest
 
 from conftest import ROOT
 from bhrt import abi, lib
-from host_sources import host_core, host_feature
+from host_sources import hip_sources, host_core, host_feature
 import kerr_rule as kr
 
 CSRC = os.path.join(ROOT, "raytracing-engine-in-c_amd", "csrc")
@@ -67,10 +67,18 @@ def test_host_core_does_not_name_the_launcher():
     assert os.path.join(CSRC, "kerr.c") not in host_core()
     for f in ("kerr.c", "kerr.hip", "bhrt_kernel.h"):
         assert "bhrt_launch_kerr(" in open(os.path.join(CSRC, f)).read(), f
-    # the colour and sky functions are shared through one header, not copied
-    for f in ("geodesic.hip", "kerr.hip"):
-        text = open(os.path.join(CSRC, f)).read()
-        assert '#include "bhrt_colour.h"' in text and "void sky_lookup(" not in text, f
+    # the colour and sky functions are shared through one header, not copied: every .hip that
+    # calls one includes bhrt_colour.h, itself or through the trace core, and defines none
+    colour, core = '#include "bhrt_colour.h"', '#include "bhrt_trace_core.h"'
+    text = open(os.path.join(CSRC, "bhrt_trace_core.h")).read()
+    assert colour in text and "void sky_lookup(" not in text
+    users = []
+    for path in hip_sources():
+        text = open(path).read()
+        if re.search(r"\b(sky_lookup|store_colour|colour_sky|colour_of|colour_of_sky)\b", text):
+            users.append(os.path.basename(path))
+            assert (colour in text or core in text) and "void sky_lookup(" not in text, path
+    assert {"geodesic.hip", "frames.hip", "kerr.hip"} <= set(users), users
 
 
 # ---- the rule against closed forms ----

@@ -66,7 +66,7 @@ def test_host_core_does_not_name_the_launcher():
         assert "bhrt_launch_sky" not in open(f).read(), f
     assert os.path.join(CSRC, "sky.c") in host_feature()
     assert os.path.join(CSRC, "sky.c") not in host_core()
-    for f in ("sky.c", "geodesic.hip", "bhrt_kernel.h"):
+    for f in ("sky.c", "frames.hip", "bhrt_kernel.h"):
         assert "bhrt_launch_sky(" in open(os.path.join(CSRC, f)).read(), f
 
 

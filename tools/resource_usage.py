@@ -7,9 +7,11 @@ Template arguments are printed as METHOD DISK SPIN0 FAR HUGE INL [ACC]."""
 import os, re, subprocess, sys
 
 src = os.path.join(os.path.dirname(__file__), "..", "raytracing-engine-in-c_amd", "csrc")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--offload-device-only",
-       "-c", "geodesic.hip", "-o", "/tmp/_ru.co", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
-out = subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
+out = ""
+for unit in ("geodesic.hip", "paths.hip"):  # k_trace, k_paths
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--offload-device-only",
+           "-c", unit, "-o", "/tmp/_ru.co", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
+    out += subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
 rows, cur = {}, None
 for l in out.splitlines():
     m = re.search(r"Function Name: (\S+)", l)

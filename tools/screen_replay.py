@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What does the disk screen of the C2 trace loop (geodesic.hip disk_cand) decide, and how early?
+"""What does the disk screen of the C2 trace loop (bhrt_trace_core.h disk_cand) decide, and how early?
 
 Replays the C2 scene's RK4 iteration in numpy as tools/shift_deltas.py does (literal
 ray_derivatives, raytracer.c:44-154), and with it the Cartesian point of every iteration, the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How large are the angle shifts of the C2 trace loop (geodesic.hip shift_or_eval, shift_chain)?
+"""How large are the angle shifts of the C2 trace loop (bhrt_trace_core.h shift_or_eval, shift_chain)?
 
 The a = 0 RK4 iteration takes six sin/cos by angle addition from a nearby known angle: stage 2,
 3, 4 of ray_derivatives' theta (= state[1]) from stage 1 (delta = h/2 k1, h/2 k2, h k3 of

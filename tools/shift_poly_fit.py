@@ -1,5 +1,5 @@
 """Minimax-style (weighted least squares on Chebyshev nodes, mpmath) fits of sin(d) and
-cos(d) - 1 on |d| <= D for the short shift polynomials of geodesic.hip (sincos_shift).
+cos(d) - 1 on |d| <= D for the short shift polynomials of bhrt_trace_core.h (sincos_shift).
 Usage: python tools/shift_poly_fit.py 0.0625  -> coefficients (double) and max abs error, for
 one, two and three coefficients each (shift_or_eval: three on 1/16; shift_chain: two on 1/64
 and one on 2^-10 = 0.0009765625)."""
