@@ -292,6 +292,30 @@ __device__ __forceinline__ bool shift_chain(double a, double s0, double c0, doub
     return fast;
 }
 
+// Narrow-first shifts from the FAR anchor. Four more shifts of the RK4
+// a = 0 iteration -- stage 2's and stage 4's theta and the advances of state[2] and state[3] --
+// start from the iteration's own start, a first-order distance away, and ran shift_or_eval's
+// three coefficients. Three of them take shift_chain<2>'s two coefficients on |delta| <= 1/64
+// first (-3 VALU each); a lane beyond the bound redoes the shift with shift_or_eval, as at the
+// chained sites. On camera B every such lane is in the first seven iterations of its ray
+// (tools/shift_deltas.py --ages, profiles/nursery/shift_ages.txt), and a wave takes fresh rays
+// about ten times in its ~3200 iterations (profiles/nursery/wave_stamps_parent.txt), so the redo
+// runs in ~2% of the wave-iterations: C2 +1.4%, C1 +2.4% same-box.
+// The advance of state[2] keeps the wide form first: with it narrow too camera B gains +2.6%,
+// but the far camera V's frame of five-iteration rays, every one beyond the bound at that site,
+// loses 3-5% -- also where a wave with no lane inside the bound skips the short polynomials, so
+// it is not their arithmetic -- and gains 7% without it (profiles/nursery/ab_parent_vs_new.txt).
+// The choice is a pure function of the lane's operands, in every instantiation alike (camera
+// frames, ray arrays, k_path, k_paths, the HUGE redo, the check kernels), so a ray's bits never
+// depend on its age, its wave-mates or the kernel that traces it.
+// BHRT_NARROW_SITES (A/B builds): bit 0 stage 2, bit 1 stage 4, bit 2 the advance of state[2],
+// bit 3 the advance of state[3]; 0 is the parent's iteration.
+#ifndef BHRT_NARROW_SITES
+#define BHRT_NARROW_SITES 11
+#endif
+constexpr int kNC2 = (BHRT_NARROW_SITES & 1) ? 2 : 0, kNC4 = (BHRT_NARROW_SITES & 2) ? 2 : 0;
+constexpr bool kNarrowY2 = (BHRT_NARROW_SITES & 4) != 0, kNarrowY3 = (BHRT_NARROW_SITES & 8) != 0;
+
 // Trig of theta (= y[1]) for one RK stage: stage 1 takes it from the previous iteration
 // (carried in Ray_), later stages shift it.
 struct Trig1 {
@@ -630,7 +654,7 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
                 o1.x = 1.0;
                 o1.ok = true;
             }
-            stage_ops<FAR, HUGE>(y20, y21, far2, sc, n, tr, o2);
+            stage_ops<FAR, HUGE, kNC2>(y20, y21, far2, sc, n, tr, o2);
             an = Trig1{y21, o2.st, o2.ct};
             ok = pair_rcp(o1, o2, w1, w2);
         }
@@ -652,7 +676,7 @@ __device__ __forceinline__ void rk4_step(double (&y)[6], double h, double h6, co
         ok = false;
         if (!FAR || !(far3 & far4)) {
             stage_ops<FAR, HUGE, 2>(yt[0], yt[1], far3, sc, n, an, o3);
-            stage_ops<FAR, HUGE>(y40, y41, far4, sc, n, tr, o4);
+            stage_ops<FAR, HUGE, kNC4>(y40, y41, far4, sc, n, tr, o4);
             t4 = Trig1{y41, o4.st, o4.ct};
             ok = pair_rcp(o3, o4, w3, w4);
         }
@@ -869,10 +893,15 @@ __device__ __forceinline__ void sph2cart_t(double r, double st, double ct, doubl
 
 // sin, cos of x from those of a, the same component one iteration earlier.
 // Per ray only (never dependent on which wave runs the ray), so results stay reproducible.
+// NARROW: two coefficients on |x - a| <= 1/64 first (shift_chain<2>, BHRT_NARROW_SITES).
+template <bool NARROW = false>
 __device__ __forceinline__ void trig_advance(double a, double x, double& s, double& c,
                                              Counters* hc) {
     double s1, c1;
-    shift_or_eval(a, s, c, x, s1, c1, hc);
+    if constexpr (NARROW)
+        shift_chain<2>(a, s, c, x, s1, c1, hc);
+    else
+        shift_or_eval(a, s, c, x, s1, c1, hc);
     s = s1;
     c = c1;
 }
@@ -1379,6 +1408,8 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
         moved = false;  // LEAPFROG / YOSHIDA: "not implemented", state unchanged (:616-624)
     }
     double x, y, z;
+    // the RK4 a = 0 iteration's advances of state[2], state[3]: BHRT_NARROW_SITES
+    constexpr bool A0 = SPIN0 && METHOD == INTEGRATOR_RK4;
     if (moved) {
         // sin, cos of state[1] feed only the a = 0 accelerations (rhs); the Kerr branch
         // (a != 0, accelerations 0) never reads them, and the compiler keeps a dead
@@ -1400,11 +1431,11 @@ __device__ __forceinline__ std::conditional_t<MASK, unsigned long long, int> ray
             R.s2 = __builtin_fma(c0, R.cd_sd, __builtin_fma(s0, R.cd_cm1, s0));
             R.c2 = __builtin_fma(-s0, R.cd_sd, __builtin_fma(c0, R.cd_cm1, c0));
         } else {
-            trig_advance(a2, R.y[2], R.s2, R.c2, hc);
+            trig_advance<A0 && kNarrowY2>(a2, R.y[2], R.s2, R.c2, hc);
         }
         // on the zero-acceleration Kerr paths state[3] never changes (zero_accel): its sin,
         // cos stay as they are
-        if (!zero_accel<SPIN0, FAR>()) trig_advance(a3, R.y[3], R.s3, R.c3, hc);
+        if (!zero_accel<SPIN0, FAR>()) trig_advance<A0 && kNarrowY3>(a3, R.y[3], R.s3, R.c3, hc);
     }
     sph2cart_t(R.y[1], R.s2, R.c2, R.s3, R.c3, x, y, z);
     const double ox = R.px, oy = R.py, oz = R.pz;

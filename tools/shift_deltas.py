@@ -24,7 +24,12 @@ holds back: lane-stages whose raw accelerations hold a |d| >= 2 or a non-finite
 value -- they take the exact |d| <= 10 test in the rare block -- and, of those, the ones the exact
 test fails too (the literal form, as before), with the same tile and mixed-wave figures.
 
-  python tools/shift_deltas.py [W H] [--cam B | --cam x,y,z,fov]   (default 480x270, B; CPU only)
+--ages adds the per-age table: for the four far-anchor sites (stage 2's and stage 4's theta, the
+advances of state[2] and state[3]) the lanes beyond 1/64 by the ray's iteration index, and the
+settled age K after which none is (profiles/nursery/shift_ages.txt).
+
+  python tools/shift_deltas.py [W H] [--cam B | --cam x,y,z,fov] [--ages]
+                                                        (default 480x270, B; CPU only)
 """
 import os
 import sys
@@ -40,6 +45,10 @@ import oracle as orc  # noqa: E402
 SITES = ("stage2", "stage3", "stage4", "adv_y1", "adv_y2", "adv_y3", "stage3_from2",
          "adv_y1_from4")
 TS = (1 / 16, 1 / 32, 1 / 64, 1 / 128, 1 / 1024)
+# the far-anchor sites (shifts from the iteration's start) and the narrow-first bound, for the
+# per-age table (--ages)
+AGE_SITES = ("stage2", "stage4", "adv_y2", "adv_y3")
+AGE_BOUND = 1 / 64
 MODEL_MAX = 1e-4  # mixed-wave model: at most this share of wave evaluations beyond the bound
 
 
@@ -100,6 +109,11 @@ def replay(cam, W, H, oracle=None):
 
     out = {s: dict(lane_over=np.zeros(len(TS)), wave_over=np.zeros(len(TS)), max=0.0)
            for s in SITES}
+    # per age (1-based iteration index of a ray: every ray of the replay starts together, so the
+    # loop index is the age): lanes alive, and lanes beyond 1/64 at each far-anchor site
+    kmax = int(iters.max()) if n else 0
+    ages = {s: np.zeros(kmax, dtype=np.int64) for s in AGE_SITES}
+    ages["alive"] = np.zeros(kmax, dtype=np.int64)
     lane_evals = wave_evals = 0
     # tiles of 8x8 pixels as waves
     px, py = np.arange(n) % W, np.arange(n) // W
@@ -126,6 +140,9 @@ def replay(cam, W, H, oracle=None):
         lane_evals += int(alive.sum())
         tiles_alive = np.bincount(tile[alive], minlength=ntile) > 0
         wave_evals += int(tiles_alive.sum())
+        ages["alive"][k] = int(alive.sum())
+        for s in AGE_SITES:
+            ages[s][k] = int((alive & (np.abs(deltas[s]) > AGE_BOUND)).sum())
         for s, dl in deltas.items():
             a = np.abs(dl)
             out[s]["max"] = max(out[s]["max"], float(a[alive].max()))
@@ -142,7 +159,33 @@ def replay(cam, W, H, oracle=None):
         y = np.where(alive, ynew, y)
     out["lane_evals"], out["wave_evals"] = lane_evals, wave_evals
     out["accel"] = accel
+    out["ages"] = ages
     return out
+
+
+def settled_age(ages):
+    """The smallest K such that no lane of age > K is beyond AGE_BOUND at any far-anchor site
+    (0: no lane ever is): the iterations a ray needs before it is "settled"."""
+    any_over = np.zeros(len(ages["alive"]), dtype=bool)
+    for s in AGE_SITES:
+        any_over |= ages[s] > 0
+    idx = np.nonzero(any_over)[0]
+    return int(idx[-1]) + 1 if len(idx) else 0
+
+
+def print_ages(res, rows=12):
+    ages = res["ages"]
+    K = settled_age(ages)
+    print(f"per age (iteration index of a ray, 1-based): lanes alive, lanes beyond 1/{round(1 / AGE_BOUND)} "
+          f"at the far-anchor sites {', '.join(AGE_SITES)}")
+    print(f"{'age':>5s} {'alive':>9s} " + " ".join(f"{s:>9s}" for s in AGE_SITES))
+    for k in range(min(max(rows, K + 2), len(ages["alive"]))):
+        print(f"{k + 1:5d} {ages['alive'][k]:9d} " + " ".join(f"{ages[s][k]:9d}" for s in AGE_SITES))
+    tail = {s: int(ages[s][rows:].sum()) for s in AGE_SITES}
+    print(f"ages {rows + 1}..{len(ages['alive'])}: " + ", ".join(f"{s} {v}" for s, v in tail.items()))
+    total = sum(int(ages[s].sum()) for s in AGE_SITES)
+    print(f"settled age K = {K}: no lane older than K iterations is beyond the bound at any of the "
+          f"four sites ({total} lane-site cases beyond it in all)")
 
 
 def mixed_wave(p):
@@ -156,6 +199,8 @@ def main(argv):
         i = argv.index("--cam")
         cam_spec = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
+    with_ages = "--ages" in argv
+    argv = [a for a in argv if a != "--ages"]
     W, H = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (480, 270)
     res = replay(parse_camera(cam_spec), W, H)
     le, we = res["lane_evals"], res["wave_evals"]
@@ -180,6 +225,8 @@ def main(argv):
         p = a["lane_" + name] / a["stage_evals"]
         print(f"  {what:66s} {p:9.2e} {a['wave_' + name] / a['wave_stage_evals']:9.2e} "
               f"{mixed_wave(p):9.2e}")
+    if with_ages:
+        print_ages(res)
 
 
 if __name__ == "__main__":
