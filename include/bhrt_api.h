@@ -970,6 +970,81 @@ int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
 int bhrt_kerr_ray_init(const BlackHoleParams* blackhole, const Vector3D* origin,
                        const Vector3D* direction, double state[6], double* E);
 
+/* ---- Physical geodesics, adaptive steps: Dormand-Prince 5(4) under config->tolerance ----
+ * The calls above have one accuracy knob, time_step, pin the step at time_step beyond 8 M and
+ * ignore config->tolerance. The bhrt_kerr_rk45_* calls trace the same rays with an embedded pair
+ * and a step chosen by tolerance: long steps in nearly flat space, short ones near the hole, and a
+ * disk point on the step's cubic instead of its chord. An opt-in path with its own kernel; every
+ * call above keeps its bits.
+ *
+ * THE ADAPTIVE RULE (tests/kerr_rk45_rule.py restates it in numpy). Time reversal, geometry,
+ * Hamiltonian, equations, initial data and the observer refusal are those of THE RULE above,
+ * unchanged; y = (x, p) is the six-component state and ydot its derivative.
+ *  Pair.       Dormand-Prince 5(4): the standard 7-stage tableau with FSAL (c = 0, 1/5, 3/10, 4/5,
+ *              8/9, 1, 1). The new point ynew is the 5th-order solution, stage 7 is ydot(ynew), and
+ *              the error vector is e = h sum_j (b5_j - b4_j) k_j. An accepted attempt's k7 is the
+ *              next attempt's k1; a rejected attempt keeps its k1. Sums run over the non-zero
+ *              weights from j = 1 up, left to right.
+ *  Trial step. h_try = min(h, r / 2) with r at the attempt's start, so no attempt leaps the hole;
+ *              the first h is time_step.
+ *  Error norm. sc_c = tol (1 + max(|y_c|, |ynew_c|)) over the six components,
+ *              err = max_c |e_c| / sc_c, tol = config->tolerance.
+ *  Controller. fac = min(5, max(0.2, 0.9 err^(-1/5))), a non-finite fac is 0.2; h = h_try fac
+ *              after an accepted and after a rejected attempt alike. Accepted iff err <= 1. Every
+ *              attempt counts: steps is the number of attempts, rejected[i] those not accepted.
+ *  After each attempt, in this order, with seg = |x_new - x_old|:
+ *              1. a non-finite ynew or err: RAY_ERROR, the ray ends on that point;
+ *              2. after a rejection the state stays and only test 6 runs;
+ *              3. with a disk: the crossing test on z_old, z_new is THE RULE's. The crossing is
+ *                 located on the cubic Hermite polynomial of z through the two end points with end
+ *                 derivatives h_try k1_z and h_try k7_z: q(theta) = q_old + theta (m0 + theta (c2
+ *                 + theta c3)), d = q_new - q_old, c2 = (3 d - 2 m0) - m1, c3 = (m0 + m1) - 2 d.
+ *                 theta = z_old / (z_old - z_new), then four Newton iterations
+ *                 theta = clamp(theta - z(theta) / z'(theta), 0, 1), a non-finite iterate keeping
+ *                 theta. q_x, q_y are the Hermite polynomials of x, y at theta; the hit test on
+ *                 q_x^2 + q_y^2 is THE RULE's: RAY_DISK, hit = (q_x, q_y, 0),
+ *                 distance += theta seg. The first hit wins;
+ *              4. r_new <= r+: RAY_HORIZON;
+ *              5. distance += seg; distance > max_ray_distance: RAY_MAX_DISTANCE;
+ *              6. attempts >= max_integration_steps: RAY_MAX_STEPS (max_integration_steps == 0: at
+ *                 the origin, with steps 0).
+ *  Outputs     are THE RULE's with two differences: sky_* of a RAY_MAX_DISTANCE ray is the EXIT
+ *              TANGENT, xdot at the end point (the FSAL stage's first three components), not the
+ *              chord -- adaptive steps are long, and a chord is not the exit direction; and the
+ *              Doppler direction of a disk hit is the unit Hermite derivative of position at theta.
+ *              Colour, the sky-map rule, rgba32f / rgba8 and determinism follow the text above with
+ *              "chord" read as this tangent.
+ *  Diagnostics (bhrt_kerr_rk45_diag): h_residual and lz_drift as above, taken over accepted points
+ *              only (the origin and every accepted ynew); rejected, int per ray.
+ *  Refusals.   Those above, each decided BEFORE ANY HIP CALL, and one more: config->tolerance must
+ *              be finite and within [1e-12, 1e-2] (below 1e-12 the error estimate is rounding
+ *              noise). time_step keeps its checks and becomes the first trial step.
+ *  Statistics. One trace launch; iterations counts attempts.
+ *  Not offered. Recorded paths of these rays: bhrt_kerr_paths* stays RK4. */
+typedef struct {
+    double* h_residual;
+    double* lz_drift;
+    int* rejected;
+} bhrt_kerr_rk45_diag;
+
+/* The four calls of "Physical geodesics" in argument types and order, stream rule included. */
+int bhrt_kerr_rk45_frame_device(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                                const SimulationConfig* config, const bhrt_camera* camera,
+                                int width, int height, const bhrt_rows* rows, int flags,
+                                const bhrt_frame_soa* device_out,
+                                const bhrt_kerr_rk45_diag* device_diag, void* hip_stream);
+int bhrt_kerr_rk45_frame(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                         const SimulationConfig* config, const bhrt_camera* camera, int width,
+                         int height, int flags, const bhrt_frame_soa* host_out,
+                         const bhrt_kerr_rk45_diag* host_diag);
+int bhrt_kerr_rk45_rays_device(const Ray* device_rays, int n, const BlackHoleParams* blackhole,
+                               const AccretionDiskParams* disk, const SimulationConfig* config,
+                               int flags, const bhrt_frame_soa* device_out,
+                               const bhrt_kerr_rk45_diag* device_diag, void* hip_stream);
+int bhrt_kerr_rk45_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
+                        const AccretionDiskParams* disk, const SimulationConfig* config, int flags,
+                        const bhrt_frame_soa* host_out, const bhrt_kerr_rk45_diag* host_diag);
+
 /* ---- Physical photon paths: batched polylines of true Kerr geodesics ----
  * bhrt_trace_paths records the parity path's rays, straight lines wherever spin != 0. These calls
  * record the rays of "Physical geodesics" above instead -- how light bends: the lensing diagram,

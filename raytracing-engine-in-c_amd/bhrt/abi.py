@@ -244,6 +244,11 @@ class KerrDiag(C.Structure):
     _fields_ = [("h_residual", C.c_void_p), ("lz_drift", C.c_void_p)]
 
 
+class KerrRk45Diag(C.Structure):
+    """bhrt_kerr_rk45_diag: KerrDiag's arrays and rejected (int32 per ray); 0 = not produced."""
+    _fields_ = [("h_residual", C.c_void_p), ("lz_drift", C.c_void_p), ("rejected", C.c_void_p)]
+
+
 class ParticlesState(C.Structure):
     """bhrt_particles_state: the host-side state of a device-resident particle system."""
     _fields_ = [("count", C.c_int32), ("device", C.c_int32), ("updates", C.c_int64)]

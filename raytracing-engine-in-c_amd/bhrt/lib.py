@@ -133,6 +133,21 @@ _PROTOS = {
     "bhrt_kerr_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                  _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                  _P(abi.FrameSoA), _P(abi.KerrDiag)]),
+    "bhrt_kerr_rk45_frame_device": (C.c_int, [_P(abi.BlackHoleParams),
+                                              _P(abi.AccretionDiskParams),
+                                              _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
+                                              C.c_int, _P(abi.Rows), C.c_int, _P(abi.FrameSoA),
+                                              _P(abi.KerrRk45Diag), C.c_void_p]),
+    "bhrt_kerr_rk45_frame": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.AccretionDiskParams),
+                                       _P(abi.SimulationConfig), _P(abi.Camera), C.c_int, C.c_int,
+                                       C.c_int, _P(abi.FrameSoA), _P(abi.KerrRk45Diag)]),
+    "bhrt_kerr_rk45_rays_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                             _P(abi.AccretionDiskParams),
+                                             _P(abi.SimulationConfig), C.c_int, _P(abi.FrameSoA),
+                                             _P(abi.KerrRk45Diag), C.c_void_p]),
+    "bhrt_kerr_rk45_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                      _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                      C.c_int, _P(abi.FrameSoA), _P(abi.KerrRk45Diag)]),
     "bhrt_kerr_paths_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                          _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
                                          C.c_int, C.c_int, C.c_int, _P(abi.Paths),
@@ -656,6 +671,55 @@ def kerr_rays(rays, bh, dk, cfg, flags=0, fields=KERR_FIELDS, diag=False):
     extra, kd = _kerr_host_diag(len(rays), diag)
     _check(load().bhrt_kerr_rays(rays.ctypes.data, len(rays), _ptr(bh), _ptr(dk), _ptr(cfg), flags,
                                  C.byref(soa), _ptr(kd)), "bhrt_kerr_rays")
+    arrays.update(extra)
+    return arrays
+
+
+def _kerr_rk45_host_diag(n, diag):
+    if not diag:
+        return {}, None
+    arrays = {"h_residual": np.zeros(n), "lz_drift": np.zeros(n),
+              "rejected": np.zeros(n, dtype=np.int32)}
+    return arrays, abi.KerrRk45Diag(*(arrays[f].ctypes.data
+                                      for f in ("h_residual", "lz_drift", "rejected")))
+
+
+def kerr_rk45_frame_device(bh, dk, cfg, cam, width, height, rows, flags, soa, diag=None,
+                           stream=None):
+    """bhrt_kerr_rk45_frame_device: kerr_frame_device with adaptive Dormand-Prince 5(4) steps
+    under cfg.tolerance; diag an abi.KerrRk45Diag of device pointers or None."""
+    _check(load().bhrt_kerr_rk45_frame_device(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width,
+                                              height, _ptr(rows), flags, C.byref(soa), _ptr(diag),
+                                              C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_rk45_frame_device")
+
+
+def kerr_rk45_frame(bh, dk, cfg, cam, width, height, flags=0, fields=KERR_FIELDS, diag=False):
+    """bhrt_kerr_rk45_frame into host numpy arrays (with diag: h_residual, lz_drift and rejected
+    as well)."""
+    arrays, soa = abi.alloc_soa(width * height, fields)
+    extra, kd = _kerr_rk45_host_diag(width * height, diag)
+    _check(load().bhrt_kerr_rk45_frame(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
+                                       flags, C.byref(soa), _ptr(kd)), "bhrt_kerr_rk45_frame")
+    arrays.update(extra)
+    return arrays
+
+
+def kerr_rk45_rays_device(rays_ptr, n, bh, dk, cfg, flags, soa, diag=None, stream=None):
+    """bhrt_kerr_rk45_rays_device: n device rays (AoS) into device SoA buffers on a hipStream_t."""
+    _check(load().bhrt_kerr_rk45_rays_device(C.c_void_p(rays_ptr), n, _ptr(bh), _ptr(dk),
+                                             _ptr(cfg), flags, C.byref(soa), _ptr(diag),
+                                             C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_rk45_rays_device")
+
+
+def kerr_rk45_rays(rays, bh, dk, cfg, flags=0, fields=KERR_FIELDS, diag=False):
+    """bhrt_kerr_rk45_rays: rays is a numpy array of abi.RAY_DTYPE; host numpy arrays back."""
+    rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+    arrays, soa = abi.alloc_soa(len(rays), fields)
+    extra, kd = _kerr_rk45_host_diag(len(rays), diag)
+    _check(load().bhrt_kerr_rk45_rays(rays.ctypes.data, len(rays), _ptr(bh), _ptr(dk), _ptr(cfg),
+                                      flags, C.byref(soa), _ptr(kd)), "bhrt_kerr_rk45_rays")
     arrays.update(extra)
     return arrays
 

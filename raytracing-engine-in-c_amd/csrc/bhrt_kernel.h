@@ -361,6 +361,20 @@ typedef struct {
 int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk, void* stream,
                            void* ev0, void* ev1);
 
+/* Physical geodesics, adaptive steps (kerr_rk45.c; kerr.hip k_kerr_rk45; the rule:
+ * include/bhrt_api.h "Physical geodesics, adaptive steps"). bhrt_kparams as for bhrt_launch_kerr
+ * (ctl[2] counts attempts); this block the constants bhrt_launch_kerr gets for the same scene
+ * (k.dt: the first trial step; k.eight_m is not read), the tolerance and the extra plane. */
+typedef struct {
+    bhrt_kerr_k k;
+    double tol;           /* config->tolerance, checked: finite, in [1e-12, 1e-2]            */
+    int* rejected;        /* bhrt_kerr_rk45_diag.rejected, device [n] or NULL                */
+} bhrt_kerr_rk45_k;
+
+/* kerr.hip; as bhrt_launch_kerr */
+int bhrt_launch_kerr_rk45(const bhrt_kparams* kp, const bhrt_kerr_rk45_k* rk, void* stream,
+                          void* ev0, void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */

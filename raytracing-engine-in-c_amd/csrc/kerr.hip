@@ -1,7 +1,9 @@
 // kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: the kernel
 // k_kerr and its launcher (the rule: include/bhrt_api.h "Physical geodesics"; tests/kerr_rule.py
 // restates it in numpy; the host side is kerr.c), and k_kerr_paths, the same rays' recorded
-// polylines (below k_kerr; the host side is kerr_paths.c).
+// polylines (below k_kerr; the host side is kerr_paths.c), and k_kerr_rk45, the same rays by adaptive
+// Dormand-Prince 5(4) attempts (below k_kerr_paths; the rule: "Physical geodesics, adaptive steps";
+// the host side is kerr_rk45.c).
 //
 // One lane per ray, FP64, fixed-step RK4 on (x, p), no LDS. A wavefront claims 64 rays at a time
 // from the launch's claim counter -- an 8x8 pixel tile of a camera frame, so that its rays live
@@ -429,7 +431,292 @@ __global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
     }
 }
 
+// The adaptive rays (the rule: include/bhrt_api.h "Physical geodesics, adaptive steps";
+// tests/kerr_rk45_rule.py restates it; the host side is kerr_rk45.c). k_kerr's shape -- the claim
+// of tiles or 64 rays, the set-up, the outputs, the colour, the statistics -- around Dormand-Prince
+// 5(4) attempts on the shared geom / deriv / finite6. FSAL: k1 and g are the accepted point's
+// stage 7 and geometry, kept across attempts (a rejected attempt keeps them), so an attempt costs
+// six geometry and derivative evaluations. The loop is a third copy for k_kerr_paths' reason:
+// k_kerr's device code is to stay what it was. Lanes of a wave take different numbers of attempts
+// and wait for the longest; there is no refill of single lanes.
+// Occupancy: two waves per SIMD, 256 registers per lane, no scratch. To fit them, what is live
+// across the stages is kept small: the sums of ynew and e over stages 1..5 are formed with stage
+// 6's point, n is formed again at the ray's exit, and the exit tangent is read from k1
+// (profiles/kerr_rk45/resource_usage.txt).
+constexpr int kRk45Waves = 2;
+
+// the standard Dormand-Prince tableau; kE = b5 - b4
+constexpr double kA21 = 1.0 / 5.0;
+constexpr double kA31 = 3.0 / 40.0, kA32 = 9.0 / 40.0;
+constexpr double kA41 = 44.0 / 45.0, kA42 = -56.0 / 15.0, kA43 = 32.0 / 9.0;
+constexpr double kA51 = 19372.0 / 6561.0, kA52 = -25360.0 / 2187.0, kA53 = 64448.0 / 6561.0,
+                 kA54 = -212.0 / 729.0;
+constexpr double kA61 = 9017.0 / 3168.0, kA62 = -355.0 / 33.0, kA63 = 46732.0 / 5247.0,
+                 kA64 = 49.0 / 176.0, kA65 = -5103.0 / 18656.0;
+constexpr double kB1 = 35.0 / 384.0, kB3 = 500.0 / 1113.0, kB4 = 125.0 / 192.0,
+                 kB5 = -2187.0 / 6784.0, kB6 = 11.0 / 84.0;
+constexpr double kE1 = 71.0 / 57600.0, kE3 = -71.0 / 16695.0, kE4 = 71.0 / 1920.0,
+                 kE5 = -17253.0 / 339200.0, kE6 = 22.0 / 525.0, kE7 = -1.0 / 40.0;
+
+__global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams kp,
+                                                              const bhrt_kerr_rk45_k rk) {
+    const int lane = threadIdx.x;
+    const bhrt_kparams& kc = in_kernarg(kp);
+    const bhrt_kerr_k& kk = rk.k;
+    const bool camera = kp.src == BHRT_SRC_CAMERA;
+    const bool diag = kk.h_residual != nullptr || kk.lz_drift != nullptr;
+    const unsigned long long units =
+        camera ? (unsigned long long)kk.ntiles : ((unsigned long long)kp.n + 63ull) / 64ull;
+    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    unsigned n_rays = 0, n_steps = 0;
+    for (;;) {
+        unsigned long long unit = 0;
+        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
+        unit = __shfl(unit, 0);
+        if (unit >= units) break;
+        // the lane's ray: id i (the output element), origin and direction (as k_kerr)
+        int i;
+        bool live;
+        double o[3], dir[3];
+        if (camera) {
+            const int ty = (int)unit / kk.tiles_x, tx = (int)unit - ty * kk.tiles_x;
+            const int px = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+            live = px < kc.cam.width && j < kk.nrows;
+            i = j * kc.cam.width + px;
+            o[0] = kc.cam.pos[0];
+            o[1] = kc.cam.pos[1];
+            o[2] = kc.cam.pos[2];
+            camera_dir(kc.cam, live ? px : 0, live ? j : 0, dir);
+        } else {
+            i = (int)unit * 64 + lane;
+            live = i < kp.n;
+            const Ray ray = kc.rays[live ? i : 0];
+            o[0] = ray.origin.x;
+            o[1] = ray.origin.y;
+            o[2] = ray.origin.z;
+            dir[0] = ray.direction.x;
+            dir[1] = ray.direction.y;
+            dir[2] = ray.direction.z;
+        }
+        double l0[3], p0[3], f0, E;
+        const bool observer =
+            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
+        {
+            double nv[3];
+            bhrt_kerr_unit(dir, nv);
+            bhrt_kerr_photon(f0, l0, nv, p0, &E);
+        }
+        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
+        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+        int steps = 0, rejected = 0;  // attempts, and those not accepted
+        double dist = 0.0;
+        Geom g = geom(y[0], y[1], y[2], kk);
+        const double lz0 = y[0] * y[4] - y[1] * y[3];
+        double hres = 0.0, lzd = 0.0;
+        if (diag && observer) hres = h_residual(g, y, E);
+        double k1[6];
+        deriv(g, y[0], y[1], y[2], y[3], y[4], y[5], E, kk, k1);
+        double hnext = kk.dt;
+        bool run = live && res < 0;
+        while (__ballot(run) != 0ull) {
+            if (run) {
+                const double h = fmin(hnext, 0.5 * g.r);  // no attempt leaps the hole
+                double k2[6], k3[6], k4[6], k5[6], k6[6], k7[6], s[6], yn[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA21 * k1[c]);
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
+#pragma unroll
+                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA31 * k1[c] + kA32 * k2[c]);
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
+#pragma unroll
+                for (int c = 0; c < 6; c++)
+                    s[c] = y[c] + h * ((kA41 * k1[c] + kA42 * k2[c]) + kA43 * k3[c]);
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
+#pragma unroll
+                for (int c = 0; c < 6; c++)
+                    s[c] = y[c] +
+                           h * (((kA51 * k1[c] + kA52 * k2[c]) + kA53 * k3[c]) + kA54 * k4[c]);
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k5);
+                // the sums of ynew and e over stages 1..5 are formed here, in the rule's order, so
+                // that k2..k5 end with stage 6's point
+                double bs[6], es[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++) {
+                    s[c] = y[c] + h * ((((kA61 * k1[c] + kA62 * k2[c]) + kA63 * k3[c]) +
+                                        kA64 * k4[c]) + kA65 * k5[c]);
+                    bs[c] = ((kB1 * k1[c] + kB3 * k3[c]) + kB4 * k4[c]) + kB5 * k5[c];
+                    es[c] = ((kE1 * k1[c] + kE3 * k3[c]) + kE4 * k4[c]) + kE5 * k5[c];
+                }
+                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k6);
+#pragma unroll
+                for (int c = 0; c < 6; c++) {
+                    yn[c] = y[c] + h * (bs[c] + kB6 * k6[c]);
+                    es[c] = es[c] + kE6 * k6[c];
+                }
+                const Geom gn = geom(yn[0], yn[1], yn[2], kk);
+                deriv(gn, yn[0], yn[1], yn[2], yn[3], yn[4], yn[5], E, kk, k7);
+                // err = max_c |e_c| / (tol (1 + max(|y_c|, |ynew_c|))), e = h sum (b5 - b4)_j k_j
+                double err = 0.0;
+                bool err_nan = false;
+#pragma unroll
+                for (int c = 0; c < 6; c++) {
+                    const double e = h * (es[c] + kE7 * k7[c]);
+                    const double q = fabs(e) / (rk.tol * (1.0 + fmax(fabs(y[c]), fabs(yn[c]))));
+                    err_nan = err_nan || q != q;
+                    err = fmax(err, q);
+                }
+                steps++;
+                if (!finite6(yn) || err_nan || !(err <= kDblMax)) {  // 1. a non-finite attempt
+                    res = RAY_ERROR;
+#pragma unroll
+                    for (int c = 0; c < 6; c++) y[c] = yn[c];
+                } else {
+                    double fac = fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
+                    if (!(fabs(fac) <= kDblMax)) fac = 0.2;
+                    hnext = h * fac;
+                    if (err <= 1.0) {  // accepted; a rejected attempt goes to test 6 alone
+                        if (diag) {    // (the accepted point: before a disk hit replaces it)
+                            hres = fmax(hres, h_residual(gn, yn, E));
+                            lzd = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - lz0);
+                        }
+                        const double cx = yn[0] - y[0], cy = yn[1] - y[1], cz = yn[2] - y[2];
+                        const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
+                        const double zo = y[2], zn = yn[2];
+                        if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
+                            // 3. the disk, on the step's cubic Hermite polynomials
+                            // q(th) = q_old + th (m0 + th (c2 + th c3))
+                            const double d3[3] = {cx, cy, cz};
+                            double m0[3], c2[3], c3[3];
+#pragma unroll
+                            for (int c = 0; c < 3; c++) {
+                                m0[c] = h * k1[c];
+                                const double m1 = h * k7[c];
+                                c2[c] = (3.0 * d3[c] - 2.0 * m0[c]) - m1;
+                                c3[c] = (m0[c] + m1) - 2.0 * d3[c];
+                            }
+                            double th = zo / (zo - zn);
+#pragma unroll
+                            for (int it = 0; it < 4; it++) {
+                                const double pz = zo + th * (m0[2] + th * (c2[2] + th * c3[2]));
+                                const double dz = m0[2] + th * (2.0 * c2[2] + th * (3.0 * c3[2]));
+                                const double tn = th - pz / dz;
+                                if (fabs(tn) <= kDblMax) th = fmin(1.0, fmax(0.0, tn));
+                            }
+                            const double qx = y[0] + th * (m0[0] + th * (c2[0] + th * c3[0]));
+                            const double qy = y[1] + th * (m0[1] + th * (c2[1] + th * c3[1]));
+                            const double s2 = qx * qx + qy * qy;
+                            if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+                                res = RAY_DISK;
+                                yn[0] = qx;
+                                yn[1] = qy;
+                                yn[2] = 0.0;
+                                dist += th * seg;
+                                // (the ray ends here: k7, the next k1, carries the tangent out)
+#pragma unroll
+                                for (int c = 0; c < 3; c++)
+                                    k7[c] = m0[c] + th * (2.0 * c2[c] + th * (3.0 * c3[c]));
+                            }
+                        }
+                        if (res < 0) {
+                            if (gn.r <= kk.r_plus) {  // 4. the horizon
+                                res = RAY_HORIZON;
+                            } else {
+                                dist += seg;  // 5. the distance
+                                if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
+                            }
+                        }
+#pragma unroll
+                        for (int c = 0; c < 6; c++) {
+                            y[c] = yn[c];
+                            k1[c] = k7[c];
+                        }
+                        g = gn;
+                    } else {
+                        rejected++;
+                    }
+                    if (res < 0 && steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 6.
+                }
+                run = res < 0;
+            }
+        }
+        if (!live) continue;
+        // the tangent at the last point: k1 is an accepted attempt's stage 7 (xdot at its end) or
+        // the Hermite derivative at a disk hit; read for RAY_DISK and RAY_MAX_DISTANCE rays only
+        const double tx = k1[0], ty = k1[1], tz = k1[2];
+        n_rays++;
+        n_steps += (unsigned)steps;
+        const bhrt_frame_soa& out = kc.out;
+        if (out.result) out.result[i] = res;
+        if (out.steps) out.steps[i] = steps;
+        if (out.hit_x) out.hit_x[i] = y[0];
+        if (out.hit_y) out.hit_y[i] = y[1];
+        if (out.hit_z) out.hit_z[i] = y[2];
+        if (out.distance) out.distance[i] = dist;
+        if (res == RAY_MAX_DISTANCE) {
+            if (out.sky_x) out.sky_x[i] = tx;
+            if (out.sky_y) out.sky_y[i] = ty;
+            if (out.sky_z) out.sky_z[i] = tz;
+        }
+        if (kk.h_residual) kk.h_residual[i] = hres;
+        if (kk.lz_drift) kk.lz_drift[i] = lzd;
+        if (rk.rejected) rk.rejected[i] = rejected;
+        if (out.rgb_r || out.rgba32f || out.rgba8) {
+            // the unit tangent at the last point: the Doppler direction of a disk hit, and what
+            // the gradient reads for a ray that left the scene; every other ray reads n
+            double ut[3];
+            const double t3[3] = {tx, ty, tz};
+            bhrt_kerr_unit(t3, ut);
+            // n again, by the set-up's own operations: not held across the attempts
+            double nv[3];
+            if (camera) {
+                camera_dir(kc.cam, i % kc.cam.width, i / kc.cam.width, dir);
+            } else {
+                const Ray ray = kc.rays[i];
+                dir[0] = ray.direction.x;
+                dir[1] = ray.direction.y;
+                dir[2] = ray.direction.z;
+            }
+            bhrt_kerr_unit(dir, nv);
+            double r, gg, b;
+            if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_DISK && res != RAY_HORIZON) {
+                // the sky-map rule on the exit tangent (k_kerr's lookup, inlined for its reason)
+                const double l2 = (tx * tx + ty * ty) + tz * tz;
+                const bool take = res == RAY_MAX_DISTANCE && fabs(tx) <= kDblMax &&
+                                  fabs(ty) <= kDblMax && fabs(tz) <= kDblMax && l2 > 0.0;
+                sky_lookup(kc.sky, take ? tx : nv[0], take ? ty : nv[1], take ? tz : nv[2], r, gg,
+                           b);
+            } else {
+                const bool tang = res == RAY_DISK || res == RAY_MAX_DISTANCE;
+                colour_of(kc.sc, res, y[0], y[1], tang ? ut[0] : nv[0], tang ? ut[1] : nv[1],
+                          tang ? ut[2] : nv[2], r, gg, b);
+            }
+            store_colour(out, i, r, gg, b);
+        }
+    }
+    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
+    if (lane == 0) {
+        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
+        if (s0) atomicAdd(kp.ctl + 1, s0);
+        if (s1) atomicAdd(kp.ctl + 2, s1);
+    }
+}
+
 }  // namespace
+
+extern "C" int bhrt_launch_kerr_rk45(const bhrt_kparams* kp, const bhrt_kerr_rk45_k* rk,
+                                     void* stream, void* ev0, void* ev1) {
+    if (kp->n <= 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
+    const long units =
+        kp->src == BHRT_SRC_CAMERA ? (long)rk->k.ntiles : ((long)kp->n + 63) / 64;
+    long blocks = resident_blocks_cached<&k_kerr_rk45>(64);
+    if (blocks > units) blocks = units;
+    if (e0) (void)hipEventRecord(e0, st);
+    k_kerr_rk45<<<(unsigned)blocks, 64, 0, st>>>(*kp, *rk);
+    if (e1) (void)hipEventRecord(e1, st);
+    return (int)hipGetLastError();
+}
 
 extern "C" int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk,
                                       void* stream, void* ev0, void* ev1) {
