@@ -1108,6 +1108,102 @@ int bhrt_kerr_paths(const Ray* rays, int n, const BlackHoleParams* blackhole,
                     int max_positions, int every, int flags, const bhrt_paths* host_paths,
                     const bhrt_frame_soa* host_hits, const bhrt_kerr_diag* host_diag);
 
+/* ---- Kerr disk emission: the redshift factor and higher-order disk images ----
+ * The calls above colour a disk pixel by the frame colour contract -- with BHRT_FLAG_DOPPLER the
+ * reference's stand-in, not a redshift -- and end every ray at its first disk crossing. The
+ * bhrt_kerr_emit_* calls give what a line-profile or EHT-style image code starts from: the
+ * frequency ratio g = E_obs / E_emit of every disk crossing, the bolometric intensity g^4 eps(r)
+ * built from it, and the disk's higher-order images (the secondary image under the shadow, the
+ * photon ring). An opt-in path with its own kernel; every call above keeps its bits.
+ *
+ * THE EMISSION RULE (tests/kerr_emit_rule.py restates it in numpy). Everything is THE ADAPTIVE RULE
+ * above -- initial data, attempts, controller, the order of the tests, the Hermite crossing point,
+ * the exit tangent -- with these differences.
+ *  Crossings.  A crossing is what test 3 finds: an accepted attempt whose Hermite point has
+ *              q_x^2 + q_y^2 within [in^2 + a~^2, out^2 + a~^2]. Crossing number k (0-based) of a ray
+ *              is recorded. K = max_crossings, 1 <= K <= BHRT_EMIT_MAX_CROSSINGS. If k + 1 < K the
+ *              ray continues from the attempt's end point ynew unchanged: distance += seg, k1 = k7,
+ *              and tests 4 to 6 run as after any accepted attempt. If k + 1 == K the ray ends as the
+ *              adaptive rule ends it: RAY_DISK, hit = (q_x, q_y, 0), distance += theta seg. One
+ *              attempt holds at most one crossing (the sign test on z_old, z_new). With K = 1 the
+ *              bhrt_frame_soa hit fields, steps and rejected are the adaptive rule's.
+ *  Redshift    of a crossing, with a = spin * mass (the physical spin, not a~; a^2 = a~^2),
+ *              s2 = q_x^2 + q_y^2 and M = mass: r = sqrt(s2 - a^2);
+ *              Omega = sqrt(M) / (r sqrt(r) + a sqrt(M)), the disk turning about +z in +phi as the
+ *              Doppler term above assumes;
+ *              N = (1 - (2M / r)(1 - a Omega)^2) - Omega^2 (r^2 + a^2), which is
+ *              -g_mu_nu u^mu u^nu / (u^t)^2 of u ~ d_t + Omega d_phi read off the Kerr-Schild metric
+ *              on the equator; g = sqrt(N) / (E + Omega L_z) with E and L_z = x p_y - y p_x of the
+ *              initial data, constants of the motion (the integrated photon is the time reverse of
+ *              the observed one, so the disk's angular velocity enters as -Omega: hence the plus
+ *              sign). g = 0 where N > 0 or E + Omega L_z > 0 fails or g is not finite: no circular
+ *              orbit there. bhrt_kerr_disk_redshift is this arithmetic on the host.
+ *  Emission.   eps(r) = pow(inner_radius / r, emissivity_index); w_k = (g_k^2)^2 eps(r_k);
+ *              intensity = sum_k w_k over the recorded crossings in order (optically and
+ *              geometrically thin), 0 for a ray without crossings.
+ *  Outputs     (bhrt_kerr_emit_out; every pointer optional): count[n], int; radius[K][n] and
+ *              redshift[K][n], plane-major, the element index k n + i formed in size_t;
+ *              intensity[n]. Elements of radius and redshift with k >= count[i] are NOT written. The
+ *              bhrt_frame_soa fields keep their adaptive-rule meaning: hit_* is the last point, or
+ *              the K-th crossing. At least one output overall, of either struct.
+ *  Colour.     A ray with count 0 gets the adaptive rule's colour: horizon black, otherwise the
+ *              gradient on the exit tangent or n, the sky-map rule under BHRT_FLAG_SKY. A ray with
+ *              crossings gets per channel clamp(gain sum_k w_k base_k, 0, 1), base_k the frame
+ *              colour contract's disk colour at (q_x, q_y) of crossing k without the Doppler block.
+ *              BHRT_FLAG_DOPPLER is refused: g replaces it.
+ *  Refusals.   Each decided BEFORE ANY HIP CALL, -1 with bhrt_last_error set and nothing written:
+ *              everything bhrt_kerr_rk45_* refuses; a NULL disk; a NULL params; max_crossings
+ *              outside 1..BHRT_EMIT_MAX_CROSSINGS; emissivity_index or gain not finite or < 0;
+ *              BHRT_FLAG_DOPPLER; no output at all; (long)K * n > INT_MAX.
+ *  Determinism, statistics, streams. As for the adaptive calls: no atomic in any output, one trace
+ *              launch, iterations counts attempts, a NULL hip_stream is ordered like the legacy
+ *              default stream. The diagnostics are bhrt_kerr_rk45_diag's.
+ *  Not offered. Limb darkening, a Novikov-Thorne flux, emission inside the ISCO's plunging region
+ *              beyond g = 0, emission on the fixed-step calls or the path recorder. */
+#define BHRT_EMIT_MAX_CROSSINGS 4
+typedef struct {
+    int max_crossings;
+    double emissivity_index;
+    double gain;
+} bhrt_kerr_emit_params;
+
+typedef struct {
+    int* count;
+    double* radius;
+    double* redshift;
+    double* intensity;
+} bhrt_kerr_emit_out;
+
+/* The four calls of "Physical geodesics, adaptive steps" with the emission's parameters and outputs
+ * (device or host arrays, as the call's other outputs; emit_out may be NULL). */
+int bhrt_kerr_emit_frame_device(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                                const SimulationConfig* config, const bhrt_camera* camera,
+                                int width, int height, const bhrt_rows* rows, int flags,
+                                const bhrt_frame_soa* device_out,
+                                const bhrt_kerr_rk45_diag* device_diag,
+                                const bhrt_kerr_emit_params* params,
+                                const bhrt_kerr_emit_out* device_emit, void* hip_stream);
+int bhrt_kerr_emit_frame(const BlackHoleParams* blackhole, const AccretionDiskParams* disk,
+                         const SimulationConfig* config, const bhrt_camera* camera, int width,
+                         int height, int flags, const bhrt_frame_soa* host_out,
+                         const bhrt_kerr_rk45_diag* host_diag,
+                         const bhrt_kerr_emit_params* params, const bhrt_kerr_emit_out* host_emit);
+int bhrt_kerr_emit_rays_device(const Ray* device_rays, int n, const BlackHoleParams* blackhole,
+                               const AccretionDiskParams* disk, const SimulationConfig* config,
+                               int flags, const bhrt_frame_soa* device_out,
+                               const bhrt_kerr_rk45_diag* device_diag,
+                               const bhrt_kerr_emit_params* params,
+                               const bhrt_kerr_emit_out* device_emit, void* hip_stream);
+int bhrt_kerr_emit_rays(const Ray* rays, int n, const BlackHoleParams* blackhole,
+                        const AccretionDiskParams* disk, const SimulationConfig* config, int flags,
+                        const bhrt_frame_soa* host_out, const bhrt_kerr_rk45_diag* host_diag,
+                        const bhrt_kerr_emit_params* params, const bhrt_kerr_emit_out* host_emit);
+/* g of the Redshift paragraph for a crossing at Boyer-Lindquist radius `radius` of a photon with
+ * constants E and lz, on the host with the device's operations. 0 and *g, or -1 (nothing written)
+ * for a NULL argument or a bad blackhole as above. No HIP call. */
+int bhrt_kerr_disk_redshift(const BlackHoleParams* blackhole, double radius, double E, double lz,
+                            double* g);
+
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);
 

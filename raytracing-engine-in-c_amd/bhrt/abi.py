@@ -249,6 +249,27 @@ class KerrRk45Diag(C.Structure):
     _fields_ = [("h_residual", C.c_void_p), ("lz_drift", C.c_void_p), ("rejected", C.c_void_p)]
 
 
+EMIT_MAX_CROSSINGS = 4  # BHRT_EMIT_MAX_CROSSINGS
+
+
+class KerrEmitParams(C.Structure):
+    """bhrt_kerr_emit_params: K = max_crossings (1..EMIT_MAX_CROSSINGS), the emissivity's index q
+    of eps(r) = (inner_radius / r)^q, and the colour's gain."""
+    _fields_ = [("max_crossings", C.c_int), ("emissivity_index", C.c_double), ("gain", C.c_double)]
+
+    def __init__(self, max_crossings=1, emissivity_index=3.0, gain=1.0):
+        super().__init__(max_crossings, emissivity_index, gain)
+
+
+EMIT_FIELDS = ("count", "radius", "redshift", "intensity")
+
+
+class KerrEmitOut(C.Structure):
+    """bhrt_kerr_emit_out: count [n] int32, radius and redshift [K][n], intensity [n] (device or
+    host, as the call's outputs); 0 = not produced."""
+    _fields_ = [(f, C.c_void_p) for f in EMIT_FIELDS]
+
+
 class ParticlesState(C.Structure):
     """bhrt_particles_state: the host-side state of a device-resident particle system."""
     _fields_ = [("count", C.c_int32), ("device", C.c_int32), ("updates", C.c_int64)]

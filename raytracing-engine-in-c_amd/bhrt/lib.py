@@ -148,6 +148,27 @@ _PROTOS = {
     "bhrt_kerr_rk45_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                       _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
                                       C.c_int, _P(abi.FrameSoA), _P(abi.KerrRk45Diag)]),
+    "bhrt_kerr_emit_frame_device": (C.c_int, [_P(abi.BlackHoleParams),
+                                              _P(abi.AccretionDiskParams),
+                                              _P(abi.SimulationConfig), _P(abi.Camera), C.c_int,
+                                              C.c_int, _P(abi.Rows), C.c_int, _P(abi.FrameSoA),
+                                              _P(abi.KerrRk45Diag), _P(abi.KerrEmitParams),
+                                              _P(abi.KerrEmitOut), C.c_void_p]),
+    "bhrt_kerr_emit_frame": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.AccretionDiskParams),
+                                       _P(abi.SimulationConfig), _P(abi.Camera), C.c_int, C.c_int,
+                                       C.c_int, _P(abi.FrameSoA), _P(abi.KerrRk45Diag),
+                                       _P(abi.KerrEmitParams), _P(abi.KerrEmitOut)]),
+    "bhrt_kerr_emit_rays_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                             _P(abi.AccretionDiskParams),
+                                             _P(abi.SimulationConfig), C.c_int, _P(abi.FrameSoA),
+                                             _P(abi.KerrRk45Diag), _P(abi.KerrEmitParams),
+                                             _P(abi.KerrEmitOut), C.c_void_p]),
+    "bhrt_kerr_emit_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
+                                      _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
+                                      C.c_int, _P(abi.FrameSoA), _P(abi.KerrRk45Diag),
+                                      _P(abi.KerrEmitParams), _P(abi.KerrEmitOut)]),
+    "bhrt_kerr_disk_redshift": (C.c_int, [_P(abi.BlackHoleParams), C.c_double, C.c_double,
+                                          C.c_double, _P(C.c_double)]),
     "bhrt_kerr_paths_device": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                          _P(abi.AccretionDiskParams), _P(abi.SimulationConfig),
                                          C.c_int, C.c_int, C.c_int, _P(abi.Paths),
@@ -722,6 +743,77 @@ def kerr_rk45_rays(rays, bh, dk, cfg, flags=0, fields=KERR_FIELDS, diag=False):
                                       flags, C.byref(soa), _ptr(kd)), "bhrt_kerr_rk45_rays")
     arrays.update(extra)
     return arrays
+
+
+def _kerr_emit_host(n, params, fill):
+    """Host arrays of a bhrt_kerr_emit_out for n rays (radius, redshift [K, n] holding `fill`) and
+    the struct pointing at them."""
+    K = int(params.max_crossings) if params is not None else 1
+    K = min(max(K, 1), abi.EMIT_MAX_CROSSINGS)     # (a refused K still gets arrays to point at)
+    arrays = {"count": np.zeros(n, dtype=np.int32), "radius": np.full((K, n), fill, dtype=np.float64),
+              "redshift": np.full((K, n), fill, dtype=np.float64), "intensity": np.zeros(n)}
+    return arrays, abi.KerrEmitOut(*(arrays[f].ctypes.data for f in abi.EMIT_FIELDS))
+
+
+def kerr_emit_frame_device(bh, dk, cfg, cam, width, height, rows, flags, soa, params, emit,
+                           diag=None, stream=None):
+    """bhrt_kerr_emit_frame_device: kerr_rk45_frame_device with up to params.max_crossings recorded
+    disk crossings per ray; emit an abi.KerrEmitOut of device pointers (or None), diag an
+    abi.KerrRk45Diag or None."""
+    _check(load().bhrt_kerr_emit_frame_device(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width,
+                                              height, _ptr(rows), flags, _ptr(soa), _ptr(diag),
+                                              _ptr(params), _ptr(emit),
+                                              C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_emit_frame_device")
+
+
+def kerr_emit_frame(bh, dk, cfg, cam, width, height, params, flags=0, fields=KERR_FIELDS,
+                    diag=False, fill=np.nan):
+    """bhrt_kerr_emit_frame into host numpy arrays: the frame fields asked for, count, radius and
+    redshift [K, n] (elements beyond a ray's count keep `fill`), intensity, and with diag
+    h_residual, lz_drift and rejected."""
+    arrays, soa = abi.alloc_soa(width * height, fields)
+    extra, kd = _kerr_rk45_host_diag(width * height, diag)
+    em, eo = _kerr_emit_host(width * height, params, fill)
+    _check(load().bhrt_kerr_emit_frame(_ptr(bh), _ptr(dk), _ptr(cfg), _ptr(cam), width, height,
+                                       flags, C.byref(soa), _ptr(kd), _ptr(params), C.byref(eo)),
+           "bhrt_kerr_emit_frame")
+    arrays.update(extra)
+    arrays.update(em)
+    return arrays
+
+
+def kerr_emit_rays_device(rays_ptr, n, bh, dk, cfg, flags, soa, params, emit, diag=None,
+                          stream=None):
+    """bhrt_kerr_emit_rays_device: n device rays (AoS) into device buffers on a hipStream_t."""
+    _check(load().bhrt_kerr_emit_rays_device(C.c_void_p(rays_ptr), n, _ptr(bh), _ptr(dk),
+                                             _ptr(cfg), flags, _ptr(soa), _ptr(diag), _ptr(params),
+                                             _ptr(emit), C.c_void_p(stream) if stream else None),
+           "bhrt_kerr_emit_rays_device")
+
+
+def kerr_emit_rays(rays, bh, dk, cfg, params, flags=0, fields=KERR_FIELDS, diag=False,
+                   fill=np.nan):
+    """bhrt_kerr_emit_rays: rays is a numpy array of abi.RAY_DTYPE; host numpy arrays back."""
+    rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE)
+    arrays, soa = abi.alloc_soa(len(rays), fields)
+    extra, kd = _kerr_rk45_host_diag(len(rays), diag)
+    em, eo = _kerr_emit_host(len(rays), params, fill)
+    _check(load().bhrt_kerr_emit_rays(rays.ctypes.data, len(rays), _ptr(bh), _ptr(dk), _ptr(cfg),
+                                      flags, C.byref(soa), _ptr(kd), _ptr(params), C.byref(eo)),
+           "bhrt_kerr_emit_rays")
+    arrays.update(extra)
+    arrays.update(em)
+    return arrays
+
+
+def kerr_disk_redshift(bh, radius, E, lz):
+    """bhrt_kerr_disk_redshift: g = E_obs / E_emit of a disk crossing at Boyer-Lindquist `radius`
+    for a photon with constants E and lz, on the host (0 where no circular orbit exists)."""
+    g = C.c_double()
+    _check(load().bhrt_kerr_disk_redshift(_ptr(bh), float(radius), float(E), float(lz),
+                                          C.byref(g)), "bhrt_kerr_disk_redshift")
+    return g.value
 
 
 def kerr_paths_device(rays_ptr, n, bh, dk, cfg, max_positions, every, flags, paths, hits=None,

@@ -375,6 +375,22 @@ typedef struct {
 int bhrt_launch_kerr_rk45(const bhrt_kparams* kp, const bhrt_kerr_rk45_k* rk, void* stream,
                           void* ev0, void* ev1);
 
+/* Kerr disk emission (kerr_emit.c; kerr.hip k_kerr_emit; the rule: include/bhrt_api.h "Kerr disk
+ * emission"). bhrt_kparams as for bhrt_launch_kerr_rk45 (sc.flags never has BHRT_FLAG_DOPPLER;
+ * sc.disk_in is the emissivity's reference radius); this block the adaptive launch's, the
+ * emission's parameters and its outputs. */
+typedef struct {
+    bhrt_kerr_rk45_k rk;
+    int max_crossings;    /* K, checked: 1..BHRT_EMIT_MAX_CROSSINGS                          */
+    double q, gain;       /* emissivity_index, gain; checked: finite, >= 0                   */
+    double spin_a;        /* spin * mass, the physical spin (-rk.k.a)                        */
+    bhrt_kerr_emit_out out; /* device arrays; NULL fields skipped; radius, redshift [K][n]   */
+} bhrt_kerr_emit_k;
+
+/* kerr.hip; as bhrt_launch_kerr */
+int bhrt_launch_kerr_emit(const bhrt_kparams* kp, const bhrt_kerr_emit_k* ek, void* stream,
+                          void* ev0, void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */
