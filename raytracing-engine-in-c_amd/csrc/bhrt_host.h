@@ -244,6 +244,55 @@ int bhrt_kerr_rays_check(const Ray* rays, int n, const BlackHoleParams* bh,
                          const AccretionDiskParams* dk, const SimulationConfig* cfg, int flags,
                          const bhrt_frame_soa* out, bhrt_kerr_k* k);
 int bhrt_kerr_observer(const bhrt_kerr_k* k, const Vector3D* o, long i);
+/* a camera call's own arguments -- the camera, the size, the row shard -- refused under the
+ * family's prefix `who` ("kerr", "kerr_rk45", "kerr_emit"): 0 and the shard's rows, or -1 */
+int bhrt_kerr_frame_check(const char* who, const bhrt_camera* cam, int W, int H,
+                          const bhrt_rows* rows, int* nrows);
+/* One checked launch of a frame / ray-array tracer (kerr.c, kerr_rk45.c, kerr_emit.c), for its
+ * run under the stream rule: what the three families share. A family with more arguments puts
+ * this first in a struct of its own. */
+typedef struct {
+    const BlackHoleParams* bh;
+    const AccretionDiskParams* dk;
+    const SimulationConfig* cfg;
+    const bhrt_camera* cam; /* NULL: a ray array */
+    int W, H, nrows;
+    const bhrt_rows* rows;
+    const Ray* d_rays;
+    int n;
+    int flags;
+    const bhrt_frame_soa* out;
+    double *h_residual, *lz_drift; /* the diagnostics' planes or NULL */
+    const bhrt_kerr_k* k;
+} bhrt_kerr_call;
+/* kp and the bhrt_kerr_k part of the launch's second argument from the call: the colour's scene
+ * and sky map, the camera (rows, tiles) or the rays, the outputs, the diagnostics' pointers. -1
+ * with the error set where bhrt_fill_scene refuses. */
+int bhrt_kerr_fill(const bhrt_kerr_call* a, bhrt_kparams* kp, bhrt_kerr_k* k);
+/* The host forms' staging. A family's planes beside the bhrt_frame_soa fields are rows of a table,
+ * in the order of their places in the context's buffer and of their copies. */
+typedef struct {
+    void* host;   /* the caller's array; NULL: not asked for (its place is kept, no copy is made) */
+    void* dev;    /* the address of a pointer VARIABLE (a double* or int* object, never an integer
+                   * or a struct) that is set to the device plane, or to NULL where host is NULL;
+                   * it is written and read as bytes (memcpy), whatever its pointee type */
+    size_t bytes;
+    int preload;  /* the kernel writes only part of it: the device plane starts from `host` */
+} bhrt_kerr_plane;
+/* the pieces (kerr_paths.c stages its paths itself around them): the buffer bytes of the fields
+ * asked for in hout and of every plane; their carving from *p with the uploads of sky_* and of the
+ * preload planes on st; the copies back after the stream was synchronised */
+size_t bhrt_kerr_stage_bytes(const bhrt_frame_soa* hout, long n, const bhrt_kerr_plane* pl,
+                             int npl);
+int bhrt_kerr_stage_carve(char** p, hipStream_t st, const bhrt_frame_soa* hout, long n,
+                          bhrt_frame_soa* dout, const bhrt_kerr_plane* pl, int npl);
+int bhrt_kerr_stage_back(const bhrt_frame_soa* hout, long n, const bhrt_frame_soa* dout,
+                         const bhrt_kerr_plane* pl, int npl);
+/* a whole host form: `a` with the host out and n rays in all -- `rays` on the host, or NULL for a
+ * camera call. Sizes and carves the context's buffer, uploads the rays, runs body(c, st, arg) with
+ * a->d_rays, a->out and the planes' pointers set to the device's, synchronises and copies back. */
+int bhrt_kerr_host(bhrt_kerr_call* a, const Ray* rays, long n, const bhrt_kerr_plane* pl, int npl,
+                   bhrt_stream_body body, const void* arg);
 /* bhrt_kerr_rays_device's launch for arguments that passed bhrt_kerr_rays_check (k: its
  * constants), on `st` of context c without the NULL-stream rule */
 int bhrt_kerr_rays_on_device(devctx_t* c, hipStream_t st, const Ray* d_rays, int n,

@@ -21,7 +21,8 @@
 #include "bhrt_host.h"
 #include "kerr_init.h"
 
-/* The checks below are shared with kerr_paths.c through bhrt_host.h. */
+/* The checks below are shared with kerr_paths.c, kerr_rk45.c and kerr_emit.c through
+ * bhrt_host.h, and so are the call struct, its filling and the host forms' staging further down. */
 /* the scene's constants, or -1 with the error set; no HIP call */
 int bhrt_kerr_scene(const BlackHoleParams* bh, const AccretionDiskParams* dk,
                     const SimulationConfig* cfg, bhrt_kerr_k* k) {
@@ -99,25 +100,32 @@ int bhrt_kerr_observer(const bhrt_kerr_k* k, const Vector3D* o, long i) {
     return -1;
 }
 
+int bhrt_kerr_frame_check(const char* who, const bhrt_camera* cam, int W, int H,
+                          const bhrt_rows* rows, int* nrows) {
+    if (!cam) {
+        bhrt_set_err("%s: camera must not be NULL", who);
+        return -1;
+    }
+    if (W < 1 || H < 1) {
+        bhrt_set_err("%s: invalid size %d x %d", who, W, H);
+        return -1;
+    }
+    *nrows = bhrt_shard_rows(H, rows);
+    if (*nrows < 0 || (long)*nrows * W > 0x7fffffffL) {
+        bhrt_set_err("%s: invalid row sharding or frame too large (%d x %d)", who, W, H);
+        return -1;
+    }
+    return 0;
+}
+
 /* a camera call's checks: 0 and the shard's rows, or -1 */
 static int kerr_frame_check(const BlackHoleParams* bh, const AccretionDiskParams* dk,
                             const SimulationConfig* cfg, const bhrt_camera* cam, int W, int H,
                             const bhrt_rows* rows, int flags, const bhrt_frame_soa* out,
                             bhrt_kerr_k* k, int* nrows) {
-    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags)) return -1;
-    if (!cam) {
-        bhrt_set_err("kerr: camera must not be NULL");
+    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags) ||
+        bhrt_kerr_frame_check("kerr", cam, W, H, rows, nrows))
         return -1;
-    }
-    if (W < 1 || H < 1) {
-        bhrt_set_err("kerr: invalid size %d x %d", W, H);
-        return -1;
-    }
-    *nrows = bhrt_shard_rows(H, rows);
-    if (*nrows < 0 || (long)*nrows * W > 0x7fffffffL) {
-        bhrt_set_err("kerr: invalid row sharding or frame too large (%d x %d)", W, H);
-        return -1;
-    }
     return bhrt_kerr_observer(k, &cam->position, -1);
 }
 
@@ -140,47 +148,36 @@ static int kerr_fn(const bhrt_kparams* kp, const void* arg, void* stream, void* 
     return bhrt_launch_kerr(kp, (const bhrt_kerr_k*)arg, stream, ev0, ev1);
 }
 
-typedef struct { /* one checked launch, for its run under the stream rule */
-    const BlackHoleParams* bh;
-    const AccretionDiskParams* dk;
-    const SimulationConfig* cfg;
-    const bhrt_camera* cam; /* NULL: a ray array */
-    int W, H, nrows;
-    const bhrt_rows* rows;
-    const Ray* d_rays;
-    int n;
-    int flags;
-    const bhrt_frame_soa* out;
-    const bhrt_kerr_diag* diag;
-    const bhrt_kerr_k* k;
-} kerr_call;
+int bhrt_kerr_fill(const bhrt_kerr_call* a, bhrt_kparams* kp, bhrt_kerr_k* k) {
+    /* the colour's constants and the sky map (the integration's are a->k) */
+    if (bhrt_fill_scene(kp, a->bh, a->dk, a->cfg, INTEGRATOR_RK4, a->flags)) return -1;
+    *k = *a->k;
+    if (a->cam) {
+        bhrt_fill_camera(kp, a->cam, a->W, a->H);
+        if (a->rows && a->rows->num_shards > 1) kp->cam.rows = *a->rows;
+        kp->n = a->nrows * a->W;
+        k->nrows = a->nrows;
+        k->tiles_x = (a->W + 7) / 8;
+        k->ntiles = k->tiles_x * ((a->nrows + 7) / 8);
+    } else {
+        kp->src = BHRT_SRC_RAYS;
+        kp->rays = a->d_rays;
+        kp->n = a->n;
+    }
+    kp->out = *a->out;
+    k->h_residual = a->h_residual;
+    k->lz_drift = a->lz_drift;
+    return 0;
+}
 
 /* the launch on `st` of context c (c NULL: the current device's, made here); device pointers */
 static int kerr_body(devctx_t* c, hipStream_t st, const void* arg) {
-    const kerr_call* a = (const kerr_call*)arg;
+    const bhrt_kerr_call* a = (const bhrt_kerr_call*)arg;
     if (!c) c = bhrt_ctx_get(bhrt_current_device());
     if (!c) return -1;
     bhrt_kparams kp;
-    /* the colour's constants and the sky map (the integration's are a->k) */
-    if (bhrt_fill_scene(&kp, a->bh, a->dk, a->cfg, INTEGRATOR_RK4, a->flags)) return -1;
-    bhrt_kerr_k k = *a->k;
-    if (a->cam) {
-        bhrt_fill_camera(&kp, a->cam, a->W, a->H);
-        if (a->rows && a->rows->num_shards > 1) kp.cam.rows = *a->rows;
-        kp.n = a->nrows * a->W;
-        k.nrows = a->nrows;
-        k.tiles_x = (a->W + 7) / 8;
-        k.ntiles = k.tiles_x * ((a->nrows + 7) / 8);
-    } else {
-        kp.src = BHRT_SRC_RAYS;
-        kp.rays = a->d_rays;
-        kp.n = a->n;
-    }
-    kp.out = *a->out;
-    if (a->diag) {
-        k.h_residual = a->diag->h_residual;
-        k.lz_drift = a->diag->lz_drift;
-    }
+    bhrt_kerr_k k;
+    if (bhrt_kerr_fill(a, &kp, &k)) return -1;
     return bhrt_ctx_launch_fn(c, &kp, st, kerr_fn, &k);
 }
 
@@ -192,7 +189,9 @@ int bhrt_kerr_frame_device(const BlackHoleParams* bh, const AccretionDiskParams*
     int nrows = 0;
     if (kerr_frame_check(bh, dk, cfg, cam, W, H, rows, flags, out, &k, &nrows)) return -1;
     if (nrows == 0) return 0;
-    const kerr_call a = {bh, dk, cfg, cam, W, H, nrows, rows, NULL, 0, flags, out, diag, &k};
+    const bhrt_kerr_call a = {bh, dk, cfg, cam, W, H, nrows, rows, NULL, 0, flags, out,
+                              diag ? diag->h_residual : NULL,
+                              diag ? diag->lz_drift : NULL, &k};
     return bhrt_on_stream(NULL, (hipStream_t)stream, kerr_body, &a);
 }
 
@@ -201,7 +200,9 @@ int bhrt_kerr_rays_device(const Ray* d_rays, int n, const BlackHoleParams* bh,
                           const bhrt_frame_soa* out, const bhrt_kerr_diag* diag, void* stream) {
     bhrt_kerr_k k;
     if (bhrt_kerr_rays_check(d_rays, n, bh, dk, cfg, flags, out, &k)) return -1;
-    const kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out, diag, &k};
+    const bhrt_kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out,
+                              diag ? diag->h_residual : NULL,
+                              diag ? diag->lz_drift : NULL, &k};
     return bhrt_on_stream(NULL, (hipStream_t)stream, kerr_body, &a);
 }
 
@@ -209,19 +210,69 @@ int bhrt_kerr_rays_on_device(devctx_t* c, hipStream_t st, const Ray* d_rays, int
                              const BlackHoleParams* bh, const AccretionDiskParams* dk,
                              const SimulationConfig* cfg, int flags, const bhrt_frame_soa* out,
                              const bhrt_kerr_diag* diag, const bhrt_kerr_k* k) {
-    const kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out, diag, k};
+    const bhrt_kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out,
+                              diag ? diag->h_residual : NULL,
+                              diag ? diag->lz_drift : NULL, k};
     return kerr_body(c, st, &a);
 }
 
-/* the host forms: `a` with host out / diag and host rays (or a camera); n rays in all */
-static int kerr_host(kerr_call* a, const Ray* rays, long n) {
+size_t bhrt_kerr_stage_bytes(const bhrt_frame_soa* hout, long n, const bhrt_kerr_plane* pl,
+                             int npl) {
+    size_t bytes = bhrt_soa_bytes(hout, n);
+    for (int i = 0; i < npl; i++) bytes += align256(pl[i].bytes);
+    return bytes;
+}
+
+int bhrt_kerr_stage_carve(char** p, hipStream_t st, const bhrt_frame_soa* hout, long n,
+                          bhrt_frame_soa* dout, const bhrt_kerr_plane* pl, int npl) {
+    const size_t N = (size_t)n;
+    bhrt_soa_carve(p, hout, n, dout);
+    for (int i = 0; i < npl; i++) { /* (a plane not asked for keeps its place: the slot is NULL) */
+        void* const d = pl[i].host ? (void*)*p : NULL;
+        memcpy(pl[i].dev, &d, sizeof d);
+        *p += align256(pl[i].bytes);
+    }
+    /* sky_* are written for RAY_MAX_DISTANCE rays alone, and a `preload` plane in part: the other
+     * elements of the caller's arrays keep what they held, so the device planes start from the
+     * caller's values */
+    double* const hsky[3] = {hout->sky_x, hout->sky_y, hout->sky_z};
+    double* const dsky[3] = {dout->sky_x, dout->sky_y, dout->sky_z};
+    for (int f = 0; f < 3; f++)
+        if (hsky[f]) HIP_TRY(hipMemcpyAsync(dsky[f], hsky[f], 8 * N, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < npl; i++)
+        if (pl[i].host && pl[i].preload) {
+            void* d;
+            memcpy(&d, pl[i].dev, sizeof d);
+            HIP_TRY(hipMemcpyAsync(d, pl[i].host, pl[i].bytes, hipMemcpyHostToDevice, st));
+        }
+    return 0;
+}
+
+int bhrt_kerr_stage_back(const bhrt_frame_soa* hout, long n, const bhrt_frame_soa* dout,
+                         const bhrt_kerr_plane* pl, int npl) {
+    /* plain synchronous copies: caller memory is never page-locked */
+    void* const* hh = (void* const*)hout;
+    for (int f = 0; f < BHRT_NFIELDS; f++)
+        if (hh[f])
+            HIP_TRY(hipMemcpy(hh[f], ((void* const*)dout)[f], k_fsize[f] * (size_t)n,
+                              hipMemcpyDeviceToHost));
+    for (int i = 0; i < npl; i++)
+        if (pl[i].host) {
+            void* d;
+            memcpy(&d, pl[i].dev, sizeof d);
+            HIP_TRY(hipMemcpy(pl[i].host, d, pl[i].bytes, hipMemcpyDeviceToHost));
+        }
+    return 0;
+}
+
+int bhrt_kerr_host(bhrt_kerr_call* a, const Ray* rays, long n, const bhrt_kerr_plane* pl, int npl,
+                   bhrt_stream_body body, const void* arg) {
     devctx_t* c = bhrt_ctx_get(bhrt_current_device());
     if (!c || bhrt_ctx_streams(c)) return -1;
     hipStream_t st = c->stream;
     const size_t N = (size_t)n;
     const bhrt_frame_soa* hout = a->out;
-    const bhrt_kerr_diag* hdiag = a->diag;
-    size_t bytes = bhrt_soa_bytes(hout, n) + 2 * align256(8 * N);
+    size_t bytes = bhrt_kerr_stage_bytes(hout, n, pl, npl);
     if (rays) bytes += align256(N * sizeof(Ray));
     if (bhrt_ensure(&c->d_ss, &c->cap_ss, bytes, 0)) return -1;
     char* p = (char*)c->d_ss;
@@ -231,31 +282,20 @@ static int kerr_host(kerr_call* a, const Ray* rays, long n) {
         p += align256(N * sizeof(Ray));
     }
     bhrt_frame_soa dout;
-    bhrt_soa_carve(&p, hout, n, &dout);
-    bhrt_kerr_diag ddiag = {NULL, NULL};
-    if (hdiag && hdiag->h_residual) ddiag.h_residual = (double*)p;
-    p += align256(8 * N);
-    if (hdiag && hdiag->lz_drift) ddiag.lz_drift = (double*)p;
+    if (bhrt_kerr_stage_carve(&p, st, hout, n, &dout, pl, npl)) return -1;
     a->out = &dout;
-    a->diag = &ddiag;
-    /* sky_* are written for RAY_MAX_DISTANCE rays alone: the other elements of the caller's
-     * arrays keep what they held, so the device planes start from the caller's values */
-    double* const hsky[3] = {hout->sky_x, hout->sky_y, hout->sky_z};
-    double* const dsky[3] = {dout.sky_x, dout.sky_y, dout.sky_z};
-    for (int f = 0; f < 3; f++)
-        if (hsky[f]) HIP_TRY(hipMemcpyAsync(dsky[f], hsky[f], 8 * N, hipMemcpyHostToDevice, st));
-    if (kerr_body(c, st, a)) return -1;
+    if (body(c, st, arg)) return -1;
     HIP_TRY(hipStreamSynchronize(st));
-    /* plain synchronous copies: caller memory is never page-locked */
-    void* const* hh = (void* const*)hout;
-    for (int f = 0; f < BHRT_NFIELDS; f++)
-        if (hh[f])
-            HIP_TRY(hipMemcpy(hh[f], ((void**)&dout)[f], k_fsize[f] * N, hipMemcpyDeviceToHost));
-    if (ddiag.h_residual)
-        HIP_TRY(hipMemcpy(hdiag->h_residual, ddiag.h_residual, 8 * N, hipMemcpyDeviceToHost));
-    if (ddiag.lz_drift)
-        HIP_TRY(hipMemcpy(hdiag->lz_drift, ddiag.lz_drift, 8 * N, hipMemcpyDeviceToHost));
-    return 0;
+    return bhrt_kerr_stage_back(hout, n, &dout, pl, npl);
+}
+
+/* the host forms: `a` with the host out and host rays (or a camera), n rays in all; the
+ * diagnostics are its two planes */
+static int kerr_host(bhrt_kerr_call* a, const bhrt_kerr_diag* diag, const Ray* rays, long n) {
+    const size_t N = (size_t)n;
+    const bhrt_kerr_plane pl[] = {{diag ? diag->h_residual : NULL, &a->h_residual, 8 * N, 0},
+                                  {diag ? diag->lz_drift : NULL, &a->lz_drift, 8 * N, 0}};
+    return bhrt_kerr_host(a, rays, n, pl, 2, kerr_body, a);
 }
 
 int bhrt_kerr_frame(const BlackHoleParams* bh, const AccretionDiskParams* dk,
@@ -264,8 +304,9 @@ int bhrt_kerr_frame(const BlackHoleParams* bh, const AccretionDiskParams* dk,
     bhrt_kerr_k k;
     int nrows = 0;
     if (kerr_frame_check(bh, dk, cfg, cam, W, H, NULL, flags, out, &k, &nrows)) return -1;
-    kerr_call a = {bh, dk, cfg, cam, W, H, nrows, NULL, NULL, 0, flags, out, diag, &k};
-    return kerr_host(&a, NULL, (long)nrows * W);
+    bhrt_kerr_call a = {bh, dk, cfg, cam, W, H, nrows, NULL, NULL, 0, flags, out,
+                        NULL, NULL, &k};
+    return kerr_host(&a, diag, NULL, (long)nrows * W);
 }
 
 int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* bh, const AccretionDiskParams* dk,
@@ -275,8 +316,9 @@ int bhrt_kerr_rays(const Ray* rays, int n, const BlackHoleParams* bh, const Accr
     if (bhrt_kerr_rays_check(rays, n, bh, dk, cfg, flags, out, &k)) return -1;
     for (long i = 0; i < n; i++)
         if (bhrt_kerr_observer(&k, &rays[i].origin, i)) return -1;
-    kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, NULL, n, flags, out, diag, &k};
-    return kerr_host(&a, rays, n);
+    bhrt_kerr_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, NULL, n, flags, out,
+                        NULL, NULL, &k};
+    return kerr_host(&a, diag, rays, n);
 }
 
 int bhrt_kerr_ray_init(const BlackHoleParams* bh, const Vector3D* origin, const Vector3D* direction,

@@ -1,23 +1,37 @@
-// kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: the kernel
-// k_kerr and its launcher (the rule: include/bhrt_api.h "Physical geodesics"; tests/kerr_rule.py
-// restates it in numpy; the host side is kerr.c), and k_kerr_paths, the same rays' recorded
-// polylines (below k_kerr; the host side is kerr_paths.c), and k_kerr_rk45, the same rays by adaptive
-// Dormand-Prince 5(4) attempts (below k_kerr_paths; the rule: "Physical geodesics, adaptive steps";
-// the host side is kerr_rk45.c), and k_kerr_emit, the adaptive rays with recorded disk crossings,
-// their redshift and intensity (below k_kerr_rk45; the rule: "Kerr disk emission"; the host side is
-// kerr_emit.c).
+// kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: four kernels
+// and their launchers.
+//   k_kerr        fixed-step RK4 rays            rule: include/bhrt_api.h "Physical geodesics",
+//                                                tests/kerr_rule.py; host side kerr.c
+//   k_kerr_paths  the same rays' polylines       "Physical photon paths", tests/kerr_paths_rule.py;
+//                                                kerr_paths.c
+//   k_kerr_rk45   adaptive Dormand-Prince 5(4)   "Physical geodesics, adaptive steps",
+//                                                tests/kerr_rk45_rule.py; kerr_rk45.c
+//   k_kerr_emit   adaptive rays with recorded    "Kerr disk emission", tests/kerr_emit_rule.py;
+//                 disk crossings                 kerr_emit.c
 //
-// One lane per ray, FP64, fixed-step RK4 on (x, p), no LDS. A wavefront claims 64 rays at a time
-// from the launch's claim counter -- an 8x8 pixel tile of a camera frame, so that its rays live
-// alike, or 64 consecutive rays of an array -- and runs them until the last has ended; there is no
-// refill of single lanes. Each stage forms the reciprocals of D, r, G and S once; the geometry at
-// a step's end point serves the horizon test, the next step's size and the next step's first
-// stage, so a step costs four geometry evaluations.
+// One lane per ray, FP64. A wavefront claims 64 rays at a time from the launch's claim counter --
+// an 8x8 pixel tile of a camera frame, so that its rays live alike, or 64 consecutive rays of an
+// array -- and runs them until the last has ended; there is no refill of single lanes. Each stage
+// forms the reciprocals of D, r, G and S once; the geometry at a step's end point serves the
+// horizon test, the next step's size and the next step's first stage.
 //
-// ONE instantiation serves camera frames and ray arrays, with and without a disk, a sky map or
-// the diagnostics (wave-uniform branches outside the stages): a ray's arithmetic is compiled once,
-// so its outputs are the same bits through every entry point. No atomic touches an output; the
-// claim counter and the statistics are the only atomics.
+// Every piece of the rule stands ONCE, as a __forceinline__ function below: the claim and the
+// statistics, a lane's ray and its initial data, the RK4 step and the tests after it, the
+// Dormand-Prince attempt, its step factor and its Hermite disk crossing, the hit stores and the
+// exit colour. A change to the rule -- the order of the tests, the 0.5 r cap, the sky rule on the exit
+// direction -- is made at one place. Two exceptions, each marked where it stands: k_kerr carries
+// rk4_step's text written out, because the call moved its bits, and k_kerr_rk45 carries the
+// claim's, the set-up's and the exit's, because the calls cost it speed. The kernels are still four __global__ functions, one
+// instantiation each, because what they keep between the pieces differs: k_kerr holds the chord and
+// the diagnostics, k_kerr_paths stores points, the adaptive kernels carry k1 across attempts, and
+// k_kerr_emit keeps in LDS what k_kerr_rk45 keeps in registers. Sharing the text does not share the
+// register allocation: each kernel inlines the pieces into its own schedule (DESIGN.md section 17;
+// profiles/kerr_shared has the resource figures and the per-kernel FP64 instruction counts, equal
+// to those of the written-out loops). Within a kernel one instantiation serves camera frames and
+// ray arrays, with and without a disk, a sky map or the diagnostics (wave-uniform branches outside
+// the stages): a ray's arithmetic is compiled once per kernel, so its outputs are the same bits
+// through every entry point. No atomic touches an output; the claim counter and the statistics are
+// the only atomics.
 #include <hip/hip_runtime.h>
 
 #include "bhrt_kernel.h"
@@ -83,6 +97,12 @@ __device__ __forceinline__ void deriv(const Geom& g, double x, double y, double 
     d[5] = hu2 * (q * drz - g.f * (2.0 * k.a2 * z) * g.iG) + fu * (drz * Ap + g.ir * pz);
 }
 
+// deriv at the point s, with the geometry formed there
+__device__ __forceinline__ void deriv_at(const double (&s)[6], double E, const bhrt_kerr_k& k,
+                                         double (&d)[6]) {
+    deriv(geom(s[0], s[1], s[2], k), s[0], s[1], s[2], s[3], s[4], s[5], E, k, d);
+}
+
 __device__ __forceinline__ bool finite6(const double (&y)[6]) {
     return fabs(y[0]) <= kDblMax && fabs(y[1]) <= kDblMax && fabs(y[2]) <= kDblMax &&
            fabs(y[3]) <= kDblMax && fabs(y[4]) <= kDblMax && fabs(y[5]) <= kDblMax;
@@ -94,6 +114,14 @@ __device__ __forceinline__ double h_residual(const Geom& g, const double (&y)[6]
     const double pp = (y[3] * y[3] + y[4] * y[4]) + y[5] * y[5];
     const double fu2 = g.f * (u * u);
     return fabs(((pp - E * E) - fu2) / ((E * E + pp) + fu2));
+}
+
+// the diagnostics at an accepted point yn (before a disk hit replaces it): the largest residual so
+// far and the drift of L_z from the initial data's
+__device__ __forceinline__ void diag_update(const Geom& gn, const double (&yn)[6], double E,
+                                            double lz0, double& hres, double& lzd) {
+    hres = fmax(hres, h_residual(gn, yn, E));
+    lzd = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - lz0);
 }
 
 // the direction of shard pixel (px, row j of the shard): calculate_ray_direction's mapping, one
@@ -113,7 +141,7 @@ __device__ __forceinline__ void camera_dir(const bhrt_camera_k& cm, int px, int 
     bhrt_kerr_unit(v, d);
 }
 
-// The launch parameters as an opaque pointer into the kernel argument segment (k_kerr's first
+// The launch parameters as an opaque pointer into the kernel argument segment (a kernel's first
 // argument starts it): the fields read through it -- the camera at a ray's set-up, the output
 // pointers, the colour's constants and the sky map at its exit -- are loaded where they are used
 // instead of being held in scalar registers across the steps.
@@ -124,6 +152,28 @@ __device__ __forceinline__ const bhrt_kparams& in_kernarg(const bhrt_kparams&) {
     return *(const bhrt_kparams*)p;
 }
 
+// ---- the claim and the statistics --------------------------------------------------------------
+
+// the units of a launch: the shard's 8x8 tiles, or the 64-ray runs of an array
+__host__ __device__ __forceinline__ unsigned long long kerr_units(int src, int n, int ntiles) {
+    return src == BHRT_SRC_CAMERA ? (unsigned long long)ntiles
+                                  : ((unsigned long long)n + 63ull) / 64ull;
+}
+
+// the wave's start stamp (ctl[8] holds the complement of the earliest)
+__device__ __forceinline__ void wave_start(unsigned long long* ctl, int lane) {
+    if (lane == 0) atomicMax(ctl + 8, ~(unsigned long long)wall_clock64());
+}
+
+// the wave's next unit from the claim counter ctl[0]; false once the launch's units are taken
+__device__ __forceinline__ bool claim(unsigned long long* ctl, int lane, unsigned long long units,
+                                      unsigned long long& unit) {
+    unit = 0;
+    if (lane == 0) unit = atomicAdd(ctl, 1ull);
+    unit = __shfl(unit, 0);
+    return unit < units;
+}
+
 __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
     unsigned long long s = v;
 #pragma unroll
@@ -131,60 +181,369 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
     return s;
 }
 
+// the wave's end stamp (ctl[9]) and its rays and steps (or attempts) into ctl[1], ctl[2]
+__device__ __forceinline__ void wave_stats(unsigned long long* ctl, int lane, unsigned n_rays,
+                                           unsigned n_steps) {
+    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
+    if (lane == 0) {
+        atomicMax(ctl + 9, (unsigned long long)wall_clock64());
+        if (s0) atomicAdd(ctl + 1, s0);
+        if (s1) atomicAdd(ctl + 2, s1);
+    }
+}
+
+// ---- a lane's ray and its initial data ---------------------------------------------------------
+
+struct LaneRay {
+    int i;      // the output element
+    bool live;  // false: a lane beyond the frame's edge or the array's end (it reads ray 0)
+    double o[3], dir[3];
+};
+
+// lane `lane` of 64 consecutive rays of an array
+__device__ __forceinline__ LaneRay array_ray(const Ray* rays, int n, unsigned long long unit,
+                                             int lane) {
+    LaneRay q;
+    const unsigned long long id = unit * 64ull + (unsigned)lane;
+    q.live = id < (unsigned long long)n;
+    q.i = (int)id;
+    const Ray ray = rays[q.live ? q.i : 0];
+    q.o[0] = ray.origin.x;
+    q.o[1] = ray.origin.y;
+    q.o[2] = ray.origin.z;
+    q.dir[0] = ray.direction.x;
+    q.dir[1] = ray.direction.y;
+    q.dir[2] = ray.direction.z;
+    return q;
+}
+
+// lane `lane` of a unit: a pixel of an 8x8 camera tile, or array_ray (kc: kp through in_kernarg)
+__device__ __forceinline__ LaneRay lane_ray(const bhrt_kparams& kc, const bhrt_kerr_k& kk,
+                                            bool camera, int n, unsigned long long unit, int lane) {
+    if (!camera) return array_ray(kc.rays, n, unit, lane);
+    LaneRay q;
+    const int ty = (int)unit / kk.tiles_x, tx = (int)unit - ty * kk.tiles_x;
+    const int px = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+    q.live = px < kc.cam.width && j < kk.nrows;
+    q.i = j * kc.cam.width + px;
+    q.o[0] = kc.cam.pos[0];
+    q.o[1] = kc.cam.pos[1];
+    q.o[2] = kc.cam.pos[2];
+    camera_dir(kc.cam, q.live ? px : 0, q.live ? j : 0, q.dir);
+    return q;
+}
+
+// n of live ray i again, by lane_ray's own operations: what a kernel that does not hold n across
+// its attempts reads at the ray's exit
+__device__ __forceinline__ void exit_n(const bhrt_kparams& kc, bool camera, int i,
+                                       double (&nv)[3]) {
+    double dir[3];
+    if (camera) {
+        camera_dir(kc.cam, i % kc.cam.width, i / kc.cam.width, dir);
+    } else {
+        const Ray ray = kc.rays[i];
+        dir[0] = ray.direction.x;
+        dir[1] = ray.direction.y;
+        dir[2] = ray.direction.z;
+    }
+    bhrt_kerr_unit(dir, nv);
+}
+
+// kerr_init.h's initial data of ray q: n, the state y = (x, p), E, whether the origin has a static
+// observer; returns the ray's class before its first step (-1: it runs)
+__device__ __forceinline__ int initial_data(const LaneRay& q, const bhrt_kerr_k& kk,
+                                            double (&nv)[3], double (&y)[6], double& E,
+                                            bool& observer) {
+    double l0[3], p0[3], f0;
+    bhrt_kerr_unit(q.dir, nv);
+    observer = bhrt_kerr_origin(q.o[0], q.o[1], q.o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0,
+                                l0) != 0;
+    bhrt_kerr_photon(f0, l0, nv, p0, &E);
+    y[0] = q.o[0];
+    y[1] = q.o[1];
+    y[2] = q.o[2];
+    y[3] = p0[0];
+    y[4] = p0[1];
+    y[5] = p0[2];
+    return observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+}
+
+// ---- the fixed-step rule: k_kerr, k_kerr_paths -------------------------------------------------
+
+// one RK4 step from y (geometry g) to yn; a step costs four geometry evaluations with the end
+// point's, which the caller forms for the tests and the next step. k_kerr_paths calls this;
+// k_kerr holds the same text written out (its comment says why): keep the two in step.
+__device__ __forceinline__ void rk4_step(const Geom& g, const double (&y)[6], double E,
+                                         const bhrt_kerr_k& kk, double (&yn)[6]) {
+    const double h = kk.dt * fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
+    const double hh = 0.5 * h;
+    double k1[6], k2[6], k3[6], k4[6], s[6];
+    deriv(g, y[0], y[1], y[2], y[3], y[4], y[5], E, kk, k1);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k1[c];
+    deriv_at(s, E, kk, k2);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k2[c];
+    deriv_at(s, E, kk, k3);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + h * k3[c];
+    deriv_at(s, E, kk, k4);
+    const double h6 = h / 6.0;
+#pragma unroll
+    for (int c = 0; c < 6; c++) yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
+}
+
+// z changed sign, or reached zero, from zo to zn
+__device__ __forceinline__ bool crosses_plane(double zo, double zn) {
+    return (zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0);
+}
+
+// The tests after step number `steps` from y to yn (geometry gn), in the rule's order; returns the
+// ray's class, -1 while it runs. A disk hit replaces yn[0..2] by the hit point; `ch` gets the chord
+// and `dist` grows. `accepted` runs once a finite yn is known, before a hit replaces it.
+template <class F>
+__device__ __forceinline__ int rk4_tests(const bhrt_kerr_k& kk, const double (&y)[6],
+                                         double (&yn)[6], const Geom& gn, int steps, double& dist,
+                                         double (&ch)[3], F&& accepted) {
+    ch[0] = yn[0] - y[0];
+    ch[1] = yn[1] - y[1];
+    ch[2] = yn[2] - y[2];
+    const double seg = sqrt((ch[0] * ch[0] + ch[1] * ch[1]) + ch[2] * ch[2]);
+    const double zo = y[2], zn = yn[2];
+    int res = -1;
+    if (!finite6(yn)) return RAY_ERROR;  // 1. a non-finite state
+    accepted();
+    if (kk.has_disk && crosses_plane(zo, zn)) {
+        const double t = zo / (zo - zn);  // 2. the disk
+        const double qx = y[0] + t * ch[0], qy = y[1] + t * ch[1];
+        const double s2 = qx * qx + qy * qy;
+        if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+            res = RAY_DISK;
+            yn[0] = qx;
+            yn[1] = qy;
+            yn[2] = 0.0;
+            dist += t * seg;
+        }
+    }
+    if (res < 0) {
+        if (gn.r <= kk.r_plus) {  // 3. the horizon
+            res = RAY_HORIZON;
+        } else {
+            dist += seg;  // 4. the distance
+            if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
+            else if (steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 5.
+        }
+    }
+    return res;
+}
+
+// ---- the adaptive rule: k_kerr_rk45, k_kerr_emit -----------------------------------------------
+
+// the standard Dormand-Prince tableau; kE = b5 - b4
+constexpr double kA21 = 1.0 / 5.0;
+constexpr double kA31 = 3.0 / 40.0, kA32 = 9.0 / 40.0;
+constexpr double kA41 = 44.0 / 45.0, kA42 = -56.0 / 15.0, kA43 = 32.0 / 9.0;
+constexpr double kA51 = 19372.0 / 6561.0, kA52 = -25360.0 / 2187.0, kA53 = 64448.0 / 6561.0,
+                 kA54 = -212.0 / 729.0;
+constexpr double kA61 = 9017.0 / 3168.0, kA62 = -355.0 / 33.0, kA63 = 46732.0 / 5247.0,
+                 kA64 = 49.0 / 176.0, kA65 = -5103.0 / 18656.0;
+constexpr double kB1 = 35.0 / 384.0, kB3 = 500.0 / 1113.0, kB4 = 125.0 / 192.0,
+                 kB5 = -2187.0 / 6784.0, kB6 = 11.0 / 84.0;
+constexpr double kE1 = 71.0 / 57600.0, kE3 = -71.0 / 16695.0, kE4 = 71.0 / 1920.0,
+                 kE5 = -17253.0 / 339200.0, kE6 = 22.0 / 525.0, kE7 = -1.0 / 40.0;
+
+// an attempt's size: the controller's, and no attempt leaps the hole
+__device__ __forceinline__ double attempt_size(double hnext, const Geom& g) {
+    return fmin(hnext, 0.5 * g.r);
+}
+
+// One Dormand-Prince 5(4) attempt of size h from y, whose stage 1 is k1 (FSAL: the accepted point's
+// stage 7, kept across attempts): stages 2..7, the new point yn with its geometry gn and stage k7,
+// and the error norm err = max_c |e_c| / (tol (1 + max(|y_c|, |ynew_c|))),
+// e = h sum (b5 - b4)_j k_j
+// (err_nan: a quotient was NaN, which fmax would drop). Six geometry and derivative evaluations.
+// To keep what is live across the stages small -- the adaptive kernels use every register of their
+// two-wave bound -- the sums of ynew and e over stages 1..5 are formed with stage 6's point, in the
+// rule's order, so that k2..k5 end there.
+__device__ __forceinline__ double dp_attempt(const double (&y)[6], const double (&k1)[6], double h,
+                                             double E, const bhrt_kerr_k& kk, double tol,
+                                             double (&yn)[6], Geom& gn, double (&k7)[6],
+                                             bool& err_nan) {
+    double k2[6], k3[6], k4[6], k5[6], k6[6], s[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA21 * k1[c]);
+    deriv_at(s, E, kk, k2);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA31 * k1[c] + kA32 * k2[c]);
+    deriv_at(s, E, kk, k3);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s[c] = y[c] + h * ((kA41 * k1[c] + kA42 * k2[c]) + kA43 * k3[c]);
+    deriv_at(s, E, kk, k4);
+#pragma unroll
+    for (int c = 0; c < 6; c++)
+        s[c] = y[c] + h * (((kA51 * k1[c] + kA52 * k2[c]) + kA53 * k3[c]) + kA54 * k4[c]);
+    deriv_at(s, E, kk, k5);
+    double bs[6], es[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        s[c] = y[c] + h * ((((kA61 * k1[c] + kA62 * k2[c]) + kA63 * k3[c]) +
+                            kA64 * k4[c]) + kA65 * k5[c]);
+        bs[c] = ((kB1 * k1[c] + kB3 * k3[c]) + kB4 * k4[c]) + kB5 * k5[c];
+        es[c] = ((kE1 * k1[c] + kE3 * k3[c]) + kE4 * k4[c]) + kE5 * k5[c];
+    }
+    deriv_at(s, E, kk, k6);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        yn[c] = y[c] + h * (bs[c] + kB6 * k6[c]);
+        es[c] = es[c] + kE6 * k6[c];
+    }
+    gn = geom(yn[0], yn[1], yn[2], kk);
+    deriv(gn, yn[0], yn[1], yn[2], yn[3], yn[4], yn[5], E, kk, k7);
+    double err = 0.0;
+    err_nan = false;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        const double e = h * (es[c] + kE7 * k7[c]);
+        const double q = fabs(e) / (tol * (1.0 + fmax(fabs(y[c]), fabs(yn[c]))));
+        err_nan = err_nan || q != q;
+        err = fmax(err, q);
+    }
+    return err;
+}
+
+// the factor of the next attempt's size after a finite err
+__device__ __forceinline__ double step_factor(double err) {
+    double fac = fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
+    if (!(fabs(fac) <= kDblMax)) fac = 0.2;
+    return fac;
+}
+
+// Where an accepted attempt of size h from y to yn crosses z = 0, on the step's cubic Hermite
+// polynomials q(th) = q_old + th (m0 + th (c2 + th c3)) between the tangents k1 and k7: four
+// Newton iterations from the chord's crossing, kept within [0, 1].
+struct Crossing {
+    double m0[3], c2[3], c3[3];
+    double th, qx, qy, s2;  // the parameter, the point (z = 0) and q_x^2 + q_y^2
+
+    // the ray ends at the crossing: yn becomes the point and k7, the next k1, carries the
+    // Hermite tangent there out
+    __device__ __forceinline__ void end_ray(double (&yn)[6], double (&k7)[6]) const {
+        yn[0] = qx;
+        yn[1] = qy;
+        yn[2] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) k7[c] = m0[c] + th * (2.0 * c2[c] + th * (3.0 * c3[c]));
+    }
+};
+
+__device__ __forceinline__ Crossing hermite_crossing(double h, const double (&y)[6],
+                                                     const double (&yn)[6],
+                                                     const double (&k1)[6],
+                                                     const double (&k7)[6]) {
+    Crossing x;
+    const double d3[3] = {yn[0] - y[0], yn[1] - y[1], yn[2] - y[2]};
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        x.m0[c] = h * k1[c];
+        const double m1 = h * k7[c];
+        x.c2[c] = (3.0 * d3[c] - 2.0 * x.m0[c]) - m1;
+        x.c3[c] = (x.m0[c] + m1) - 2.0 * d3[c];
+    }
+    const double zo = y[2], zn = yn[2];
+    double th = zo / (zo - zn);
+#pragma unroll
+    for (int it = 0; it < 4; it++) {
+        const double pz = zo + th * (x.m0[2] + th * (x.c2[2] + th * x.c3[2]));
+        const double dz = x.m0[2] + th * (2.0 * x.c2[2] + th * (3.0 * x.c3[2]));
+        const double tn = th - pz / dz;
+        if (fabs(tn) <= kDblMax) th = fmin(1.0, fmax(0.0, tn));
+    }
+    x.th = th;
+    x.qx = y[0] + th * (x.m0[0] + th * (x.c2[0] + th * x.c3[0]));
+    x.qy = y[1] + th * (x.m0[1] + th * (x.c2[1] + th * x.c3[1]));
+    x.s2 = x.qx * x.qx + x.qy * x.qy;
+    return x;
+}
+
+// ---- a ray's exit ------------------------------------------------------------------------------
+
+// the hit record of ray i; `sky`: the exit chord (k_kerr) or tangent (the adaptive kernels),
+// stored for RAY_MAX_DISTANCE rays alone
+__device__ __forceinline__ void store_hit(const bhrt_frame_soa& out, const bhrt_kerr_k& kk, int i,
+                                          int res, int steps, const double (&y)[6], double dist,
+                                          const double (&sky)[3], double hres, double lzd) {
+    if (out.result) out.result[i] = res;
+    if (out.steps) out.steps[i] = steps;
+    if (out.hit_x) out.hit_x[i] = y[0];
+    if (out.hit_y) out.hit_y[i] = y[1];
+    if (out.hit_z) out.hit_z[i] = y[2];
+    if (out.distance) out.distance[i] = dist;
+    if (res == RAY_MAX_DISTANCE) {
+        if (out.sky_x) out.sky_x[i] = sky[0];
+        if (out.sky_y) out.sky_y[i] = sky[1];
+        if (out.sky_z) out.sky_z[i] = sky[2];
+    }
+    if (kk.h_residual) kk.h_residual[i] = hres;
+    if (kk.lz_drift) kk.lz_drift[i] = lzd;
+}
+
+__device__ __forceinline__ bool wants_colour(const bhrt_frame_soa& out) {
+    return out.rgb_r || out.rgba32f || out.rgba8;
+}
+
+// The colour of a ray of class res that ended at (hx, hy, .) with exit direction t, the last chord
+// (k_kerr) or the tangent at the last point (the adaptive kernels); n is its initial direction.
+// With a sky map, a ray that is neither a disk hit nor in the hole looks up t if it left the scene
+// and t counts (finite, squared length > 0), else n. Inlined here, not colour_of_sky's call: that
+// function returns through memory. Without one, colour_of reads the unit of t -- the Doppler
+// direction of a disk hit, and what the gradient reads for a ray that left the scene -- and n for
+// every other ray.
+__device__ __forceinline__ void exit_colour(const bhrt_kparams& kc, int res, double hx, double hy,
+                                            const double (&nv)[3], const double (&t)[3],
+                                            double& r, double& g, double& b) {
+    double ut[3];
+    bhrt_kerr_unit(t, ut);
+    if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_DISK && res != RAY_HORIZON) {
+        const double l2 = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
+        const bool take = res == RAY_MAX_DISTANCE && fabs(t[0]) <= kDblMax &&
+                          fabs(t[1]) <= kDblMax && fabs(t[2]) <= kDblMax && l2 > 0.0;
+        sky_lookup(kc.sky, take ? t[0] : nv[0], take ? t[1] : nv[1], take ? t[2] : nv[2], r, g, b);
+    } else {
+        const bool exit_dir = res == RAY_DISK || res == RAY_MAX_DISTANCE;
+        colour_of(kc.sc, res, hx, hy, exit_dir ? ut[0] : nv[0], exit_dir ? ut[1] : nv[1],
+                  exit_dir ? ut[2] : nv[2], r, g, b);
+    }
+}
+
+// ---- the kernels -------------------------------------------------------------------------------
+
+// Fixed-step RK4 on (x, p), no LDS. The diagnostics are a wave-uniform branch outside the stages.
 __global__ __launch_bounds__(64) void k_kerr(const bhrt_kparams kp, const bhrt_kerr_k kk) {
     const int lane = threadIdx.x;
     const bhrt_kparams& kc = in_kernarg(kp);
     const bool camera = kp.src == BHRT_SRC_CAMERA;
     const bool diag = kk.h_residual != nullptr || kk.lz_drift != nullptr;
-    const unsigned long long units =
-        camera ? (unsigned long long)kk.ntiles : ((unsigned long long)kp.n + 63ull) / 64ull;
-    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    const unsigned long long units = kerr_units(kp.src, kp.n, kk.ntiles);
+    wave_start(kp.ctl, lane);
     unsigned n_rays = 0, n_steps = 0;
-    for (;;) {
-        unsigned long long unit = 0;
-        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
-        unit = __shfl(unit, 0);
-        if (unit >= units) break;
-        // the lane's ray: id i (the output element), origin and direction
-        int i;
-        bool live;
-        double o[3], dir[3];
-        if (camera) {
-            const int ty = (int)unit / kk.tiles_x, tx = (int)unit - ty * kk.tiles_x;
-            const int px = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-            live = px < kc.cam.width && j < kk.nrows;
-            i = j * kc.cam.width + px;
-            o[0] = kc.cam.pos[0];
-            o[1] = kc.cam.pos[1];
-            o[2] = kc.cam.pos[2];
-            camera_dir(kc.cam, live ? px : 0, live ? j : 0, dir);
-        } else {
-            i = (int)unit * 64 + lane;
-            live = i < kp.n;
-            const Ray ray = kc.rays[live ? i : 0];
-            o[0] = ray.origin.x;
-            o[1] = ray.origin.y;
-            o[2] = ray.origin.z;
-            dir[0] = ray.direction.x;
-            dir[1] = ray.direction.y;
-            dir[2] = ray.direction.z;
-        }
-        double nv[3], l0[3], p0[3], f0, E;
-        bhrt_kerr_unit(dir, nv);
-        const bool observer =
-            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
-        bhrt_kerr_photon(f0, l0, nv, p0, &E);
-        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
-        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+    for (unsigned long long unit; claim(kp.ctl, lane, units, unit);) {
+        const LaneRay q = lane_ray(kc, kk, camera, kp.n, unit, lane);
+        double nv[3], y[6], E;
+        bool observer;
+        int res = initial_data(q, kk, nv, y, E, observer);
         int steps = 0;
-        double dist = 0.0, cx = 0.0, cy = 0.0, cz = 0.0;
+        double dist = 0.0, ch[3] = {0.0, 0.0, 0.0};  // the distance, the last step's chord
         Geom g = geom(y[0], y[1], y[2], kk);
         const double lz0 = y[0] * y[4] - y[1] * y[3];
         double hres = 0.0, lzd = 0.0;
         if (diag && observer) hres = h_residual(g, y, E);
-        bool run = live && res < 0;
+        bool run = q.live && res < 0;
         while (__ballot(run) != 0ull) {
             if (run) {
+                // rk4_step's text, written out: called as the function, the stages compile to the
+                // same FP64 instruction counts but another choice of which product of an
+                // a*b + c*d is fused, and this kernel's hit points are no longer the bits they
+                // were (profiles/kerr_shared/bitexact.txt). A change to rk4_step is made here too.
                 const double h = kk.dt * fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
                 const double hh = 0.5 * h;
                 double k1[6], k2[6], k3[6], k4[6], s[6];
@@ -204,104 +563,31 @@ __global__ __launch_bounds__(64) void k_kerr(const bhrt_kparams kp, const bhrt_k
                 for (int c = 0; c < 6; c++)
                     yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
                 steps++;
-                cx = yn[0] - y[0];
-                cy = yn[1] - y[1];
-                cz = yn[2] - y[2];
-                const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
                 const Geom gn = geom(yn[0], yn[1], yn[2], kk);
-                const double zo = y[2], zn = yn[2];
-                if (!finite6(yn)) {  // 1. a non-finite state
-                    res = RAY_ERROR;
-                } else {
-                    if (diag) {  // (the accepted point: before a disk hit replaces it)
-                        hres = fmax(hres, h_residual(gn, yn, E));
-                        lzd = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - lz0);
-                    }
-                    if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
-                        const double t = zo / (zo - zn);  // 2. the disk
-                        const double qx = y[0] + t * cx, qy = y[1] + t * cy;
-                        const double s2 = qx * qx + qy * qy;
-                        if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
-                            res = RAY_DISK;
-                            yn[0] = qx;
-                            yn[1] = qy;
-                            yn[2] = 0.0;
-                            dist += t * seg;
-                        }
-                    }
-                    if (res < 0) {
-                        if (gn.r <= kk.r_plus) {  // 3. the horizon
-                            res = RAY_HORIZON;
-                        } else {
-                            dist += seg;  // 4. the distance
-                            if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
-                            else if (steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 5.
-                        }
-                    }
-                }
+                res = rk4_tests(kk, y, yn, gn, steps, dist, ch, [&] {
+                    if (diag) diag_update(gn, yn, E, lz0, hres, lzd);
+                });
 #pragma unroll
                 for (int c = 0; c < 6; c++) y[c] = yn[c];
                 g = gn;
                 run = res < 0;
             }
         }
-        if (!live) continue;
+        if (!q.live) continue;
         n_rays++;
         n_steps += (unsigned)steps;
-        const bhrt_frame_soa& out = kc.out;
-        if (out.result) out.result[i] = res;
-        if (out.steps) out.steps[i] = steps;
-        if (out.hit_x) out.hit_x[i] = y[0];
-        if (out.hit_y) out.hit_y[i] = y[1];
-        if (out.hit_z) out.hit_z[i] = y[2];
-        if (out.distance) out.distance[i] = dist;
-        if (res == RAY_MAX_DISTANCE) {
-            if (out.sky_x) out.sky_x[i] = cx;
-            if (out.sky_y) out.sky_y[i] = cy;
-            if (out.sky_z) out.sky_z[i] = cz;
-        }
-        if (kk.h_residual) kk.h_residual[i] = hres;
-        if (kk.lz_drift) kk.lz_drift[i] = lzd;
-        if (out.rgb_r || out.rgba32f || out.rgba8) {
-            // the unit chord of the last segment: the Doppler direction of a disk hit, and what
-            // the gradient reads for a ray that left the scene; every other ray reads n
-            double uc[3];
-            const double c3[3] = {cx, cy, cz};
-            bhrt_kerr_unit(c3, uc);
+        store_hit(kc.out, kk, q.i, res, steps, y, dist, ch, hres, lzd);
+        if (wants_colour(kc.out)) {
             double r, gg, b;
-            if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_DISK && res != RAY_HORIZON) {
-                // the sky-map rule: the exit chord of a ray that left the scene if it counts
-                // (finite, squared length > 0), else n. Inlined here, not colour_of_sky's call:
-                // that function returns through memory, and this kernel has one instantiation,
-                // so there is no second copy of the iterations to keep in step with
-                const double l2 = (cx * cx + cy * cy) + cz * cz;
-                const bool take = res == RAY_MAX_DISTANCE && fabs(cx) <= kDblMax &&
-                                  fabs(cy) <= kDblMax && fabs(cz) <= kDblMax && l2 > 0.0;
-                sky_lookup(kc.sky, take ? cx : nv[0], take ? cy : nv[1], take ? cz : nv[2], r, gg,
-                           b);
-            } else {
-                const bool chord = res == RAY_DISK || res == RAY_MAX_DISTANCE;
-                colour_of(kc.sc, res, y[0], y[1], chord ? uc[0] : nv[0], chord ? uc[1] : nv[1],
-                          chord ? uc[2] : nv[2], r, gg, b);
-            }
-            store_colour(out, i, r, gg, b);
+            exit_colour(kc, res, y[0], y[1], nv, ch, r, gg, b);
+            store_colour(kc.out, q.i, r, gg, b);
         }
     }
-    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
-    if (lane == 0) {
-        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
-        if (s0) atomicAdd(kp.ctl + 1, s0);
-        if (s1) atomicAdd(kp.ctl + 2, s1);
-    }
+    wave_stats(kp.ctl, lane, n_rays, n_steps);
 }
 
-// The recorded polylines of a ray array (the rule: include/bhrt_api.h "Physical photon paths";
-// tests/kerr_paths_rule.py restates it; the host side is kerr_paths.c). k_kerr's ray-array branch
-// and k_kerr's step -- geom, deriv, finite6, the five tests in the rule's order, kerr_init.h's
-// initial data -- without colour, sky map or diagnostics, and with the point stores. The loop is
-// written out a second time, not shared through an inline function: with the step factored out of
-// k_kerr the compiler allocated k_kerr's registers differently, and k_kerr's
-// device code is to stay what it was.
+// The recorded polylines of a ray array: k_kerr's rays and k_kerr's step and tests, without
+// colour, sky map or diagnostics, and with the point stores.
 // Point j of the full path is the position after step j (steps == j; q_0 the origin), the hit
 // point for the step that hits the disk. A lane keeps the multiples of `every` (next_keep: the next
 // one) and, at its end, the last point if that was not one; `slot` counts what it stored, and
@@ -315,28 +601,15 @@ __global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
     const long long every = pk.every;
     double* const xyz = reinterpret_cast<double*>(pk.out.xyz);
     float* const xyz32 = pk.out.xyz32;
-    const unsigned long long units = ((unsigned long long)kp.n + 63ull) / 64ull;
-    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    const unsigned long long units = kerr_units(BHRT_SRC_RAYS, kp.n, 0);
+    wave_start(kp.ctl, lane);
     unsigned n_rays = 0, n_steps = 0;
-    for (;;) {
-        unsigned long long unit = 0;
-        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
-        unit = __shfl(unit, 0);
-        if (unit >= units) break;
-        const unsigned long long id = unit * 64ull + (unsigned)lane;
-        const bool live = id < (unsigned long long)kp.n;
-        const int i = live ? (int)id : 0;
-        const size_t row = (size_t)i * P;  // element index of the ray's slot 0
-        const Ray ray = kp.rays[i];
-        const double o[3] = {ray.origin.x, ray.origin.y, ray.origin.z};
-        const double dir[3] = {ray.direction.x, ray.direction.y, ray.direction.z};
-        double nv[3], l0[3], p0[3], f0, E;
-        bhrt_kerr_unit(dir, nv);
-        const bool observer =
-            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
-        bhrt_kerr_photon(f0, l0, nv, p0, &E);
-        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
-        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
+    for (unsigned long long unit; claim(kp.ctl, lane, units, unit);) {
+        const LaneRay q = array_ray(kp.rays, kp.n, unit, lane);
+        const size_t row = (size_t)(q.live ? q.i : 0) * P;  // element index of the ray's slot 0
+        double nv[3], y[6], E;
+        bool observer;
+        int res = initial_data(q, kk, nv, y, E, observer);
         int steps = 0;
         double dist = 0.0;
         Geom g = geom(y[0], y[1], y[2], kk);
@@ -358,58 +631,15 @@ __global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
             slot++;
             next_keep += every;
         };
-        if (live) emit();  // q_0, the origin as given; max_positions >= 1
-        bool run = live && res < 0;
+        if (q.live) emit();  // q_0, the origin as given; max_positions >= 1
+        bool run = q.live && res < 0;
         while (__ballot(run) != 0ull) {
             if (run) {
-                const double h = kk.dt * fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
-                const double hh = 0.5 * h;
-                double k1[6], k2[6], k3[6], k4[6], s[6];
-                deriv(g, y[0], y[1], y[2], y[3], y[4], y[5], E, kk, k1);
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k1[c];
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + hh * k2[c];
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + h * k3[c];
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
-                const double h6 = h / 6.0;
-                double yn[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++)
-                    yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
+                double yn[6], ch[3];
+                rk4_step(g, y, E, kk, yn);
                 steps++;
-                const double cx = yn[0] - y[0], cy = yn[1] - y[1], cz = yn[2] - y[2];
-                const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
                 const Geom gn = geom(yn[0], yn[1], yn[2], kk);
-                const double zo = y[2], zn = yn[2];
-                if (!finite6(yn)) {  // 1. a non-finite state
-                    res = RAY_ERROR;
-                } else {
-                    if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
-                        const double t = zo / (zo - zn);  // 2. the disk
-                        const double qx = y[0] + t * cx, qy = y[1] + t * cy;
-                        const double s2 = qx * qx + qy * qy;
-                        if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
-                            res = RAY_DISK;
-                            yn[0] = qx;
-                            yn[1] = qy;
-                            yn[2] = 0.0;
-                            dist += t * seg;
-                        }
-                    }
-                    if (res < 0) {
-                        if (gn.r <= kk.r_plus) {  // 3. the horizon
-                            res = RAY_HORIZON;
-                        } else {
-                            dist += seg;  // 4. the distance
-                            if (dist > kk.max_dist) res = RAY_MAX_DISTANCE;
-                            else if (steps >= kk.max_steps) res = RAY_MAX_STEPS;  // 5.
-                        }
-                    }
-                }
+                res = rk4_tests(kk, y, yn, gn, steps, dist, ch, [] {});
 #pragma unroll
                 for (int c = 0; c < 6; c++) y[c] = yn[c];
                 g = gn;
@@ -421,45 +651,28 @@ __global__ __launch_bounds__(64) void k_kerr_paths(const bhrt_kparams kp,
                     emit();
             }
         }
-        if (!live) continue;
+        if (!q.live) continue;
         n_rays++;
         n_steps += (unsigned)steps;
-        if (pk.out.count) pk.out.count[i] = (int)slot;
+        if (pk.out.count) pk.out.count[q.i] = (int)slot;
     }
-    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
-    if (lane == 0) {
-        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
-        if (s0) atomicAdd(kp.ctl + 1, s0);
-        if (s1) atomicAdd(kp.ctl + 2, s1);
-    }
+    wave_stats(kp.ctl, lane, n_rays, n_steps);
 }
 
-// The adaptive rays (the rule: include/bhrt_api.h "Physical geodesics, adaptive steps";
-// tests/kerr_rk45_rule.py restates it; the host side is kerr_rk45.c). k_kerr's shape -- the claim
-// of tiles or 64 rays, the set-up, the outputs, the colour, the statistics -- around Dormand-Prince
-// 5(4) attempts on the shared geom / deriv / finite6. FSAL: k1 and g are the accepted point's
-// stage 7 and geometry, kept across attempts (a rejected attempt keeps them), so an attempt costs
-// six geometry and derivative evaluations. The loop is a third copy for k_kerr_paths' reason:
-// k_kerr's device code is to stay what it was. Lanes of a wave take different numbers of attempts
-// and wait for the longest; there is no refill of single lanes.
-// Occupancy: two waves per SIMD, 256 registers per lane, no scratch. To fit them, what is live
-// across the stages is kept small: the sums of ynew and e over stages 1..5 are formed with stage
-// 6's point, n is formed again at the ray's exit, and the exit tangent is read from k1
-// (profiles/kerr_rk45/resource_usage.txt).
+// The adaptive rays: k_kerr's shape -- the claim, the set-up, the outputs, the colour, the
+// statistics -- around Dormand-Prince attempts. FSAL: k1 and g are the accepted point's stage 7 and
+// geometry, kept across attempts (a rejected attempt keeps them). Lanes of a wave take different
+// numbers of attempts and wait for the longest; there is no refill of single lanes.
+// Occupancy: two waves per SIMD, 256 registers per lane, no scratch. To fit them, n is formed again
+// at the ray's exit and the exit tangent is read from k1 (DESIGN.md section 18,
+// profiles/kerr_shared/resource_usage.txt).
+// The attempt, the step factor and the Hermite crossing are the shared functions. The claim, the
+// set-up and the exit are the shared functions' text WRITTEN OUT (wave_start / claim / wave_stats,
+// lane_ray / initial_data, store_hit / exit_n / exit_colour): through the calls this kernel
+// measured 0.45-0.75% slower at tolerance 1e-8 than before the pieces were shared, beyond the run-to-run
+// spread, with its FP64 instruction counts unchanged; with this text it is within
+// (profiles/kerr_shared/ab_parent_vs_new.txt). A change to one of those functions is made here too.
 constexpr int kRk45Waves = 2;
-
-// the standard Dormand-Prince tableau; kE = b5 - b4
-constexpr double kA21 = 1.0 / 5.0;
-constexpr double kA31 = 3.0 / 40.0, kA32 = 9.0 / 40.0;
-constexpr double kA41 = 44.0 / 45.0, kA42 = -56.0 / 15.0, kA43 = 32.0 / 9.0;
-constexpr double kA51 = 19372.0 / 6561.0, kA52 = -25360.0 / 2187.0, kA53 = 64448.0 / 6561.0,
-                 kA54 = -212.0 / 729.0;
-constexpr double kA61 = 9017.0 / 3168.0, kA62 = -355.0 / 33.0, kA63 = 46732.0 / 5247.0,
-                 kA64 = 49.0 / 176.0, kA65 = -5103.0 / 18656.0;
-constexpr double kB1 = 35.0 / 384.0, kB3 = 500.0 / 1113.0, kB4 = 125.0 / 192.0,
-                 kB5 = -2187.0 / 6784.0, kB6 = 11.0 / 84.0;
-constexpr double kE1 = 71.0 / 57600.0, kE3 = -71.0 / 16695.0, kE4 = 71.0 / 1920.0,
-                 kE5 = -17253.0 / 339200.0, kE6 = 22.0 / 525.0, kE7 = -1.0 / 40.0;
 
 __global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams kp,
                                                               const bhrt_kerr_rk45_k rk) {
@@ -477,7 +690,7 @@ __global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams
         if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
         unit = __shfl(unit, 0);
         if (unit >= units) break;
-        // the lane's ray: id i (the output element), origin and direction (as k_kerr)
+        // the lane's ray: id i (the output element), origin and direction (lane_ray's text)
         int i;
         bool live;
         double o[3], dir[3];
@@ -523,101 +736,28 @@ __global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams
         bool run = live && res < 0;
         while (__ballot(run) != 0ull) {
             if (run) {
-                const double h = fmin(hnext, 0.5 * g.r);  // no attempt leaps the hole
-                double k2[6], k3[6], k4[6], k5[6], k6[6], k7[6], s[6], yn[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA21 * k1[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA31 * k1[c] + kA32 * k2[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
-#pragma unroll
-                for (int c = 0; c < 6; c++)
-                    s[c] = y[c] + h * ((kA41 * k1[c] + kA42 * k2[c]) + kA43 * k3[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
-#pragma unroll
-                for (int c = 0; c < 6; c++)
-                    s[c] = y[c] +
-                           h * (((kA51 * k1[c] + kA52 * k2[c]) + kA53 * k3[c]) + kA54 * k4[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k5);
-                // the sums of ynew and e over stages 1..5 are formed here, in the rule's order, so
-                // that k2..k5 end with stage 6's point
-                double bs[6], es[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    s[c] = y[c] + h * ((((kA61 * k1[c] + kA62 * k2[c]) + kA63 * k3[c]) +
-                                        kA64 * k4[c]) + kA65 * k5[c]);
-                    bs[c] = ((kB1 * k1[c] + kB3 * k3[c]) + kB4 * k4[c]) + kB5 * k5[c];
-                    es[c] = ((kE1 * k1[c] + kE3 * k3[c]) + kE4 * k4[c]) + kE5 * k5[c];
-                }
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k6);
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    yn[c] = y[c] + h * (bs[c] + kB6 * k6[c]);
-                    es[c] = es[c] + kE6 * k6[c];
-                }
-                const Geom gn = geom(yn[0], yn[1], yn[2], kk);
-                deriv(gn, yn[0], yn[1], yn[2], yn[3], yn[4], yn[5], E, kk, k7);
-                // err = max_c |e_c| / (tol (1 + max(|y_c|, |ynew_c|))), e = h sum (b5 - b4)_j k_j
-                double err = 0.0;
-                bool err_nan = false;
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    const double e = h * (es[c] + kE7 * k7[c]);
-                    const double q = fabs(e) / (rk.tol * (1.0 + fmax(fabs(y[c]), fabs(yn[c]))));
-                    err_nan = err_nan || q != q;
-                    err = fmax(err, q);
-                }
+                const double h = attempt_size(hnext, g);
+                double yn[6], k7[6];
+                Geom gn;
+                bool err_nan;
+                const double err = dp_attempt(y, k1, h, E, kk, rk.tol, yn, gn, k7, err_nan);
                 steps++;
                 if (!finite6(yn) || err_nan || !(err <= kDblMax)) {  // 1. a non-finite attempt
                     res = RAY_ERROR;
 #pragma unroll
                     for (int c = 0; c < 6; c++) y[c] = yn[c];
                 } else {
-                    double fac = fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
-                    if (!(fabs(fac) <= kDblMax)) fac = 0.2;
-                    hnext = h * fac;
+                    hnext = h * step_factor(err);
                     if (err <= 1.0) {  // accepted; a rejected attempt goes to test 6 alone
-                        if (diag) {    // (the accepted point: before a disk hit replaces it)
-                            hres = fmax(hres, h_residual(gn, yn, E));
-                            lzd = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - lz0);
-                        }
+                        if (diag) diag_update(gn, yn, E, lz0, hres, lzd);
                         const double cx = yn[0] - y[0], cy = yn[1] - y[1], cz = yn[2] - y[2];
                         const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
-                        const double zo = y[2], zn = yn[2];
-                        if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
-                            // 3. the disk, on the step's cubic Hermite polynomials
-                            // q(th) = q_old + th (m0 + th (c2 + th c3))
-                            const double d3[3] = {cx, cy, cz};
-                            double m0[3], c2[3], c3[3];
-#pragma unroll
-                            for (int c = 0; c < 3; c++) {
-                                m0[c] = h * k1[c];
-                                const double m1 = h * k7[c];
-                                c2[c] = (3.0 * d3[c] - 2.0 * m0[c]) - m1;
-                                c3[c] = (m0[c] + m1) - 2.0 * d3[c];
-                            }
-                            double th = zo / (zo - zn);
-#pragma unroll
-                            for (int it = 0; it < 4; it++) {
-                                const double pz = zo + th * (m0[2] + th * (c2[2] + th * c3[2]));
-                                const double dz = m0[2] + th * (2.0 * c2[2] + th * (3.0 * c3[2]));
-                                const double tn = th - pz / dz;
-                                if (fabs(tn) <= kDblMax) th = fmin(1.0, fmax(0.0, tn));
-                            }
-                            const double qx = y[0] + th * (m0[0] + th * (c2[0] + th * c3[0]));
-                            const double qy = y[1] + th * (m0[1] + th * (c2[1] + th * c3[1]));
-                            const double s2 = qx * qx + qy * qy;
-                            if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+                        if (kk.has_disk && crosses_plane(y[2], yn[2])) {  // 3. the disk
+                            const Crossing x = hermite_crossing(h, y, yn, k1, k7);
+                            if (kk.disk_lo <= x.s2 && x.s2 <= kk.disk_hi) {
                                 res = RAY_DISK;
-                                yn[0] = qx;
-                                yn[1] = qy;
-                                yn[2] = 0.0;
-                                dist += th * seg;
-                                // (the ray ends here: k7, the next k1, carries the tangent out)
-#pragma unroll
-                                for (int c = 0; c < 3; c++)
-                                    k7[c] = m0[c] + th * (2.0 * c2[c] + th * (3.0 * c3[c]));
+                                dist += x.th * seg;
+                                x.end_ray(yn, k7);
                             }
                         }
                         if (res < 0) {
@@ -664,25 +804,22 @@ __global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams
         if (kk.lz_drift) kk.lz_drift[i] = lzd;
         if (rk.rejected) rk.rejected[i] = rejected;
         if (out.rgb_r || out.rgba32f || out.rgba8) {
-            // the unit tangent at the last point: the Doppler direction of a disk hit, and what
-            // the gradient reads for a ray that left the scene; every other ray reads n
             double ut[3];
             const double t3[3] = {tx, ty, tz};
             bhrt_kerr_unit(t3, ut);
             // n again, by the set-up's own operations: not held across the attempts
-            double nv[3];
+            double nv[3], dn[3];
             if (camera) {
-                camera_dir(kc.cam, i % kc.cam.width, i / kc.cam.width, dir);
+                camera_dir(kc.cam, i % kc.cam.width, i / kc.cam.width, dn);
             } else {
                 const Ray ray = kc.rays[i];
-                dir[0] = ray.direction.x;
-                dir[1] = ray.direction.y;
-                dir[2] = ray.direction.z;
+                dn[0] = ray.direction.x;
+                dn[1] = ray.direction.y;
+                dn[2] = ray.direction.z;
             }
-            bhrt_kerr_unit(dir, nv);
+            bhrt_kerr_unit(dn, nv);
             double r, gg, b;
             if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_DISK && res != RAY_HORIZON) {
-                // the sky-map rule on the exit tangent (k_kerr's lookup, inlined for its reason)
                 const double l2 = (tx * tx + ty * ty) + tz * tz;
                 const bool take = res == RAY_MAX_DISTANCE && fabs(tx) <= kDblMax &&
                                   fabs(ty) <= kDblMax && fabs(tz) <= kDblMax && l2 > 0.0;
@@ -704,17 +841,16 @@ __global__ __launch_bounds__(64, kRk45Waves) void k_kerr_rk45(const bhrt_kparams
     }
 }
 
-// Disk emission (the rule: include/bhrt_api.h "Kerr disk emission"; tests/kerr_emit_rule.py
-// restates it; the host side is kerr_emit.c). k_kerr_rk45's attempts, tests and exit, with the
-// disk test recording up to K crossings per ray instead of ending the ray on its first: each
-// crossing's radius and redshift (kerr_emit.h) are stored where the crossing is found -- after the
-// attempt's state update, outside the stages, and rare. k_kerr_rk45 uses every register of its
-// two-wave bound, so nothing of the emission is held in registers across the stages: the count,
-// the intensity sum and the three colour sums wait in LDS between crossings, and so does what a
-// ray touches once per accepted attempt at the most (L_z of the initial data, the distance, the two
-// diagnostics); 76 bytes per lane, each lane its own words: no barrier. The loop is a fourth copy
-// for k_kerr_paths' reason: the other kernels' device code is to stay what it was. Two waves per
-// SIMD, 256 registers, no scratch (profiles/kerr_emit/resource_usage.txt).
+// Disk emission: k_kerr_rk45's attempts, tests and exit, with the disk test recording up to K
+// crossings per ray instead of ending the ray on its first: each crossing's radius and redshift
+// (kerr_emit.h) are stored where the crossing is found -- after the attempt's state update, outside
+// the stages, and rare. k_kerr_rk45 uses every register of its two-wave bound, so nothing of the
+// emission is held in registers across the stages: the count, the intensity sum and the three
+// colour sums wait in LDS between crossings, and so does what a ray touches once per accepted
+// attempt at the most (L_z of the initial data, the distance, the two diagnostics); 76 bytes per
+// lane, each lane its own words: no barrier. That is what keeps this a kernel of its own beside
+// k_kerr_rk45. Two waves per SIMD, 256 registers, no scratch (DESIGN.md section 19,
+// profiles/kerr_shared/resource_usage.txt).
 constexpr int kEmitWaves = 2;
 
 __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams kp,
@@ -739,49 +875,19 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
     const bhrt_kerr_k& kk = rk.k;
     const bool camera = kp.src == BHRT_SRC_CAMERA;
     const bool diag = kk.h_residual != nullptr || kk.lz_drift != nullptr;
-    const unsigned long long units =
-        camera ? (unsigned long long)kk.ntiles : ((unsigned long long)kp.n + 63ull) / 64ull;
-    if (lane == 0) atomicMax(kp.ctl + 8, ~(unsigned long long)wall_clock64());
+    const unsigned long long units = kerr_units(kp.src, kp.n, kk.ntiles);
+    wave_start(kp.ctl, lane);
     unsigned n_rays = 0, n_steps = 0;
-    for (;;) {
-        unsigned long long unit = 0;
-        if (lane == 0) unit = atomicAdd(kp.ctl, 1ull);
-        unit = __shfl(unit, 0);
-        if (unit >= units) break;
-        // the lane's ray: id i (the output element), origin and direction (as k_kerr)
-        int i;
-        bool live;
-        double o[3], dir[3];
-        if (camera) {
-            const int ty = (int)unit / kk.tiles_x, tx = (int)unit - ty * kk.tiles_x;
-            const int px = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-            live = px < kc.cam.width && j < kk.nrows;
-            i = j * kc.cam.width + px;
-            o[0] = kc.cam.pos[0];
-            o[1] = kc.cam.pos[1];
-            o[2] = kc.cam.pos[2];
-            camera_dir(kc.cam, live ? px : 0, live ? j : 0, dir);
-        } else {
-            i = (int)unit * 64 + lane;
-            live = i < kp.n;
-            const Ray ray = kc.rays[live ? i : 0];
-            o[0] = ray.origin.x;
-            o[1] = ray.origin.y;
-            o[2] = ray.origin.z;
-            dir[0] = ray.direction.x;
-            dir[1] = ray.direction.y;
-            dir[2] = ray.direction.z;
-        }
-        double l0[3], p0[3], f0, E;
-        const bool observer =
-            bhrt_kerr_origin(o[0], o[1], o[2], kk.a, kk.a2, kk.two_m, kk.r_plus, &f0, l0) != 0;
+    for (unsigned long long unit; claim(kp.ctl, lane, units, unit);) {
+        const LaneRay q = lane_ray(kc, kk, camera, kp.n, unit, lane);
+        const int i = q.i;
+        double y[6], E;
+        bool observer;
+        int res;
         {
-            double nv[3];
-            bhrt_kerr_unit(dir, nv);
-            bhrt_kerr_photon(f0, l0, nv, p0, &E);
+            double nv[3];  // (not held across the attempts: exit_n)
+            res = initial_data(q, kk, nv, y, E, observer);
         }
-        double y[6] = {o[0], o[1], o[2], p0[0], p0[1], p0[2]};
-        int res = observer ? (kk.max_steps > 0 ? -1 : (int)RAY_MAX_STEPS) : (int)RAY_ERROR;
         int steps = 0, rejected = 0;  // attempts, and those not accepted
         ls.dist[lane] = 0.0;  // the distance: read and written once per accepted attempt
         Geom g = geom(y[0], y[1], y[2], kk);
@@ -798,107 +904,39 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
         ls.cnt[lane] = 0;
 #pragma unroll
         for (int c = 0; c < 4; c++) ls.sum[c][lane] = 0.0;
-        bool run = live && res < 0;
+        bool run = q.live && res < 0;
         while (__ballot(run) != 0ull) {
             if (run) {
-                const double h = fmin(hnext, 0.5 * g.r);  // no attempt leaps the hole
-                double k2[6], k3[6], k4[6], k5[6], k6[6], k7[6], s[6], yn[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA21 * k1[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k2);
-#pragma unroll
-                for (int c = 0; c < 6; c++) s[c] = y[c] + h * (kA31 * k1[c] + kA32 * k2[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k3);
-#pragma unroll
-                for (int c = 0; c < 6; c++)
-                    s[c] = y[c] + h * ((kA41 * k1[c] + kA42 * k2[c]) + kA43 * k3[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k4);
-#pragma unroll
-                for (int c = 0; c < 6; c++)
-                    s[c] = y[c] +
-                           h * (((kA51 * k1[c] + kA52 * k2[c]) + kA53 * k3[c]) + kA54 * k4[c]);
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k5);
-                // (the sums over stages 1..5 with stage 6's point, as k_kerr_rk45)
-                double bs[6], es[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    s[c] = y[c] + h * ((((kA61 * k1[c] + kA62 * k2[c]) + kA63 * k3[c]) +
-                                        kA64 * k4[c]) + kA65 * k5[c]);
-                    bs[c] = ((kB1 * k1[c] + kB3 * k3[c]) + kB4 * k4[c]) + kB5 * k5[c];
-                    es[c] = ((kE1 * k1[c] + kE3 * k3[c]) + kE4 * k4[c]) + kE5 * k5[c];
-                }
-                deriv(geom(s[0], s[1], s[2], kk), s[0], s[1], s[2], s[3], s[4], s[5], E, kk, k6);
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    yn[c] = y[c] + h * (bs[c] + kB6 * k6[c]);
-                    es[c] = es[c] + kE6 * k6[c];
-                }
-                const Geom gn = geom(yn[0], yn[1], yn[2], kk);
-                deriv(gn, yn[0], yn[1], yn[2], yn[3], yn[4], yn[5], E, kk, k7);
-                double err = 0.0;
-                bool err_nan = false;
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    const double e = h * (es[c] + kE7 * k7[c]);
-                    const double q = fabs(e) / (rk.tol * (1.0 + fmax(fabs(y[c]), fabs(yn[c]))));
-                    err_nan = err_nan || q != q;
-                    err = fmax(err, q);
-                }
+                const double h = attempt_size(hnext, g);
+                double yn[6], k7[6];
+                Geom gn;
+                bool err_nan;
+                const double err = dp_attempt(y, k1, h, E, kk, rk.tol, yn, gn, k7, err_nan);
                 steps++;
                 if (!finite6(yn) || err_nan || !(err <= kDblMax)) {  // 1. a non-finite attempt
                     res = RAY_ERROR;
 #pragma unroll
                     for (int c = 0; c < 6; c++) y[c] = yn[c];
                 } else {
-                    double fac = fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
-                    if (!(fabs(fac) <= kDblMax)) fac = 0.2;
-                    hnext = h * fac;
+                    hnext = h * step_factor(err);
                     if (err <= 1.0) {  // accepted; a rejected attempt goes to test 6 alone
-                        if (diag) {    // (the accepted point: before a disk hit replaces it)
-                            ls.diag[0][lane] = fmax(ls.diag[0][lane], h_residual(gn, yn, E));
-                            ls.diag[1][lane] = fabs((yn[0] * yn[4] - yn[1] * yn[3]) - ls.lz0[lane]);
-                        }
+                        if (diag)
+                            diag_update(gn, yn, E, ls.lz0[lane], ls.diag[0][lane],
+                                        ls.diag[1][lane]);
                         const double cx = yn[0] - y[0], cy = yn[1] - y[1], cz = yn[2] - y[2];
                         const double seg = sqrt((cx * cx + cy * cy) + cz * cz);
-                        const double zo = y[2], zn = yn[2];
                         bool crossed = false;  // (q_x^2 + q_y^2 of the crossing waits in LDS)
-                        if (kk.has_disk && ((zo > 0.0 && zn <= 0.0) || (zo < 0.0 && zn >= 0.0))) {
-                            // 3. the disk, on the step's cubic Hermite polynomials (k_kerr_rk45's)
-                            const double d3[3] = {cx, cy, cz};
-                            double m0[3], c2[3], c3[3];
-#pragma unroll
-                            for (int c = 0; c < 3; c++) {
-                                m0[c] = h * k1[c];
-                                const double m1 = h * k7[c];
-                                c2[c] = (3.0 * d3[c] - 2.0 * m0[c]) - m1;
-                                c3[c] = (m0[c] + m1) - 2.0 * d3[c];
-                            }
-                            double th = zo / (zo - zn);
-#pragma unroll
-                            for (int it = 0; it < 4; it++) {
-                                const double pz = zo + th * (m0[2] + th * (c2[2] + th * c3[2]));
-                                const double dz = m0[2] + th * (2.0 * c2[2] + th * (3.0 * c3[2]));
-                                const double tn = th - pz / dz;
-                                if (fabs(tn) <= kDblMax) th = fmin(1.0, fmax(0.0, tn));
-                            }
-                            const double qx = y[0] + th * (m0[0] + th * (c2[0] + th * c3[0]));
-                            const double qy = y[1] + th * (m0[1] + th * (c2[1] + th * c3[1]));
-                            const double s2 = qx * qx + qy * qy;
-                            if (kk.disk_lo <= s2 && s2 <= kk.disk_hi) {
+                        if (kk.has_disk && crosses_plane(y[2], yn[2])) {  // 3. the disk
+                            const Crossing x = hermite_crossing(h, y, yn, k1, k7);
+                            if (kk.disk_lo <= x.s2 && x.s2 <= kk.disk_hi) {
                                 // crossing number cnt (the K-th ends the ray); it is recorded
                                 // below, once the attempt's stage vectors are dead
                                 crossed = true;
-                                ls.sq[lane] = s2;
+                                ls.sq[lane] = x.s2;
                                 if (ls.cnt[lane] + 1 == ec.max_crossings) {
                                     res = RAY_DISK;
-                                    yn[0] = qx;
-                                    yn[1] = qy;
-                                    yn[2] = 0.0;
-                                    ls.dist[lane] = ls.dist[lane] + th * seg;
-                                    // (the ray ends here: k7, the next k1, carries the tangent out)
-#pragma unroll
-                                    for (int c = 0; c < 3; c++)
-                                        k7[c] = m0[c] + th * (2.0 * c2[c] + th * (3.0 * c3[c]));
+                                    ls.dist[lane] = ls.dist[lane] + x.th * seg;
+                                    x.end_ray(yn, k7);
                                 }
                             }
                         }
@@ -931,7 +969,7 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
                             const double g2 = gz * gz;
                             const double w = (g2 * g2) * pow(kc.sc.disk_in / rad, ec.q);
                             ls.sum[0][lane] = ls.sum[0][lane] + w;
-                            if (kc.out.rgb_r || kc.out.rgba32f || kc.out.rgba8) {
+                            if (wants_colour(kc.out)) {
                                 double br, bg, bb;
                                 // (the disk colour reads sqrt(q_x^2 + q_y^2) alone)
                                 colour_of(kc.sc, RAY_DISK, sqrt(sq), 0.0, 0.0, 0.0, 0.0, br, bg,
@@ -950,30 +988,18 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
                 run = res < 0;
             }
         }
-        if (!live) continue;
+        if (!q.live) continue;
         // the tangent at the last point (as k_kerr_rk45: read from k1)
-        const double tx = k1[0], ty = k1[1], tz = k1[2];
+        const double tg[3] = {k1[0], k1[1], k1[2]};
         n_rays++;
         n_steps += (unsigned)steps;
-        const bhrt_frame_soa& out = kc.out;
-        if (out.result) out.result[i] = res;
-        if (out.steps) out.steps[i] = steps;
-        if (out.hit_x) out.hit_x[i] = y[0];
-        if (out.hit_y) out.hit_y[i] = y[1];
-        if (out.hit_z) out.hit_z[i] = y[2];
-        if (out.distance) out.distance[i] = ls.dist[lane];
-        if (res == RAY_MAX_DISTANCE) {
-            if (out.sky_x) out.sky_x[i] = tx;
-            if (out.sky_y) out.sky_y[i] = ty;
-            if (out.sky_z) out.sky_z[i] = tz;
-        }
-        if (kk.h_residual) kk.h_residual[i] = ls.diag[0][lane];
-        if (kk.lz_drift) kk.lz_drift[i] = ls.diag[1][lane];
+        store_hit(kc.out, kk, i, res, steps, y, ls.dist[lane], tg, ls.diag[0][lane],
+                  ls.diag[1][lane]);
         if (rk.rejected) rk.rejected[i] = rejected;
         const int cnt = ls.cnt[lane];
         if (ec.out.count) ec.out.count[i] = cnt;
         if (ec.out.intensity) ec.out.intensity[i] = ls.sum[0][lane];
-        if (out.rgb_r || out.rgba32f || out.rgba8) {
+        if (wants_colour(kc.out)) {
             double r, gg, b;
             if (cnt > 0) {
 #pragma clang fp contract(off)
@@ -981,99 +1007,57 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
                 gg = clampd(ec.gain * ls.sum[2][lane], 0.0, 1.0);
                 b = clampd(ec.gain * ls.sum[3][lane], 0.0, 1.0);
             } else {
-                // the adaptive rule's colour (k_kerr_rk45's exit; a ray without crossings is
-                // never RAY_DISK)
-                double ut[3];
-                const double t3[3] = {tx, ty, tz};
-                bhrt_kerr_unit(t3, ut);
+                // the adaptive rule's colour. A ray without crossings is never RAY_DISK, so
+                // colour_of is colour_sky here and the disk colour is not compiled a second time
+                __builtin_assume(res != RAY_DISK);
                 double nv[3];
-                if (camera) {
-                    camera_dir(kc.cam, i % kc.cam.width, i / kc.cam.width, dir);
-                } else {
-                    const Ray ray = kc.rays[i];
-                    dir[0] = ray.direction.x;
-                    dir[1] = ray.direction.y;
-                    dir[2] = ray.direction.z;
-                }
-                bhrt_kerr_unit(dir, nv);
-                if ((kc.sc.flags & BHRT_FLAG_SKY) && res != RAY_HORIZON) {
-                    const double l2 = (tx * tx + ty * ty) + tz * tz;
-                    const bool take = res == RAY_MAX_DISTANCE && fabs(tx) <= kDblMax &&
-                                      fabs(ty) <= kDblMax && fabs(tz) <= kDblMax && l2 > 0.0;
-                    sky_lookup(kc.sky, take ? tx : nv[0], take ? ty : nv[1], take ? tz : nv[2], r,
-                               gg, b);
-                } else {
-                    const bool tang = res == RAY_MAX_DISTANCE;
-                    colour_sky(res, tang ? ut[1] : nv[1], r, gg, b);
-                }
+                exit_n(kc, camera, i, nv);
+                exit_colour(kc, res, y[0], y[1], nv, tg, r, gg, b);
             }
-            store_colour(out, i, r, gg, b);
+            store_colour(kc.out, i, r, gg, b);
         }
     }
-    const unsigned long long s0 = wave_sum(n_rays), s1 = wave_sum(n_steps);
-    if (lane == 0) {
-        atomicMax(kp.ctl + 9, (unsigned long long)wall_clock64());
-        if (s0) atomicAdd(kp.ctl + 1, s0);
-        if (s1) atomicAdd(kp.ctl + 2, s1);
-    }
+    wave_stats(kp.ctl, lane, n_rays, n_steps);
+}
+
+// One launch: as many one-wave workgroups as are resident at once (bhrt_launch.h), at most one
+// per unit, with ev0 / ev1 recorded around the kernel; 0 or a hipError_t value.
+template <auto KERNEL, class Arg>
+int launch(const bhrt_kparams* kp, const Arg* arg, long units, void* stream, void* ev0,
+           void* ev1) {
+    if (kp->n <= 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
+    long blocks = resident_blocks_cached<KERNEL>(64);
+    if (blocks > units) blocks = units;
+    if (e0) (void)hipEventRecord(e0, st);
+    KERNEL<<<(unsigned)blocks, 64, 0, st>>>(*kp, *arg);
+    if (e1) (void)hipEventRecord(e1, st);
+    return (int)hipGetLastError();
 }
 
 }  // namespace
 
 extern "C" int bhrt_launch_kerr_emit(const bhrt_kparams* kp, const bhrt_kerr_emit_k* ek,
                                      void* stream, void* ev0, void* ev1) {
-    if (kp->n <= 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
-    const long units =
-        kp->src == BHRT_SRC_CAMERA ? (long)ek->rk.k.ntiles : ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks_cached<&k_kerr_emit>(64);
-    if (blocks > units) blocks = units;
-    if (e0) (void)hipEventRecord(e0, st);
-    k_kerr_emit<<<(unsigned)blocks, 64, 0, st>>>(*kp, *ek);
-    if (e1) (void)hipEventRecord(e1, st);
-    return (int)hipGetLastError();
+    const long units = (long)kerr_units(kp->src, kp->n, ek->rk.k.ntiles);
+    return launch<&k_kerr_emit>(kp, ek, units, stream, ev0, ev1);
 }
 
 extern "C" int bhrt_launch_kerr_rk45(const bhrt_kparams* kp, const bhrt_kerr_rk45_k* rk,
                                      void* stream, void* ev0, void* ev1) {
-    if (kp->n <= 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
-    const long units =
-        kp->src == BHRT_SRC_CAMERA ? (long)rk->k.ntiles : ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks_cached<&k_kerr_rk45>(64);
-    if (blocks > units) blocks = units;
-    if (e0) (void)hipEventRecord(e0, st);
-    k_kerr_rk45<<<(unsigned)blocks, 64, 0, st>>>(*kp, *rk);
-    if (e1) (void)hipEventRecord(e1, st);
-    return (int)hipGetLastError();
+    const long units = (long)kerr_units(kp->src, kp->n, rk->k.ntiles);
+    return launch<&k_kerr_rk45>(kp, rk, units, stream, ev0, ev1);
 }
 
 extern "C" int bhrt_launch_kerr_paths(const bhrt_kparams* kp, const bhrt_kerr_paths_k* pk,
                                       void* stream, void* ev0, void* ev1) {
-    if (kp->n <= 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
-    const long units = ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks_cached<&k_kerr_paths>(64);  // one-wave workgroups (bhrt_launch.h)
-    if (blocks > units) blocks = units;
-    if (e0) (void)hipEventRecord(e0, st);
-    k_kerr_paths<<<(unsigned)blocks, 64, 0, st>>>(*kp, *pk);
-    if (e1) (void)hipEventRecord(e1, st);
-    return (int)hipGetLastError();
+    const long units = (long)kerr_units(BHRT_SRC_RAYS, kp->n, 0);
+    return launch<&k_kerr_paths>(kp, pk, units, stream, ev0, ev1);
 }
 
 extern "C" int bhrt_launch_kerr(const bhrt_kparams* kp, const bhrt_kerr_k* kk, void* stream,
                                 void* ev0, void* ev1) {
-    if (kp->n <= 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
-    const long units = kp->src == BHRT_SRC_CAMERA ? (long)kk->ntiles : ((long)kp->n + 63) / 64;
-    long blocks = resident_blocks_cached<&k_kerr>(64);
-    if (blocks > units) blocks = units;
-    if (e0) (void)hipEventRecord(e0, st);
-    k_kerr<<<(unsigned)blocks, 64, 0, st>>>(*kp, *kk);
-    if (e1) (void)hipEventRecord(e1, st);
-    return (int)hipGetLastError();
+    const long units = (long)kerr_units(kp->src, kp->n, kk->ntiles);
+    return launch<&k_kerr>(kp, kk, units, stream, ev0, ev1);
 }

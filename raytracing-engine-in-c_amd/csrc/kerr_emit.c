@@ -8,9 +8,11 @@
  * The calls are kerr_rk45.c's in shape: the argument checks -- kerr.c's own, shared through
  * bhrt_host.h, the tolerance's and the emission's; every refusal is decided before any HIP call --
  * and one launch on the caller's stream through bhrt_ctx_launch_fn, timed and counted like a trace
- * launch (iterations: attempts). The host forms run the same launch into the context's cached
- * device buffer and copy back what was asked for. radius and redshift elements beyond a ray's
- * count are not written, so their device planes start from the caller's values.
+ * launch (iterations: attempts). The call struct's shared part, the filling of the launch's
+ * arguments and the host forms' staging are kerr.c's (bhrt_kerr_call, bhrt_kerr_fill,
+ * bhrt_kerr_host); this file adds the emission's parameters and its four output planes. radius
+ * and redshift elements beyond a ray's count are not written, so their device planes start from
+ * the caller's values.
  *
  * A file of its own (the Makefile's HOST_FEATURE): it names its own launcher and no other.
  */
@@ -70,27 +72,16 @@ static int emit_bad(const AccretionDiskParams* dk, const SimulationConfig* cfg, 
     return 0;
 }
 
-/* a camera call's checks (kerr_rk45.c's and the emission's): 0 and the shard's rows */
+/* a camera call's checks (kerr.c's and the emission's): 0 and the shard's rows */
 static int emit_frame_check(const BlackHoleParams* bh, const AccretionDiskParams* dk,
                             const SimulationConfig* cfg, const bhrt_camera* cam, int W, int H,
                             const bhrt_rows* rows, int flags, const bhrt_frame_soa* out,
                             const bhrt_kerr_emit_params* ep, const bhrt_kerr_emit_out* eo,
                             bhrt_kerr_k* k, int* nrows) {
-    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags)) return -1;
-    if (!cam) {
-        bhrt_set_err("kerr_emit: camera must not be NULL");
+    if (bhrt_kerr_scene(bh, dk, cfg, k) || bhrt_kerr_out_bad(out, flags) ||
+        bhrt_kerr_frame_check("kerr_emit", cam, W, H, rows, nrows) ||
+        emit_bad(dk, cfg, flags, out, ep, eo, (long)*nrows * W))
         return -1;
-    }
-    if (W < 1 || H < 1) {
-        bhrt_set_err("kerr_emit: invalid size %d x %d", W, H);
-        return -1;
-    }
-    *nrows = bhrt_shard_rows(H, rows);
-    if (*nrows < 0 || (long)*nrows * W > 0x7fffffffL) {
-        bhrt_set_err("kerr_emit: invalid row sharding or frame too large (%d x %d)", W, H);
-        return -1;
-    }
-    if (emit_bad(dk, cfg, flags, out, ep, eo, (long)*nrows * W)) return -1;
     return bhrt_kerr_observer(k, &cam->position, -1);
 }
 
@@ -109,21 +100,13 @@ static int emit_fn(const bhrt_kparams* kp, const void* arg, void* stream, void* 
 }
 
 typedef struct { /* one checked launch, for its run under the stream rule */
-    const BlackHoleParams* bh;
-    const AccretionDiskParams* dk;
-    const SimulationConfig* cfg;
-    const bhrt_camera* cam; /* NULL: a ray array */
-    int W, H, nrows;
-    const bhrt_rows* rows;
-    const Ray* d_rays;
-    int n;
-    int flags;
-    const bhrt_frame_soa* out;
-    const bhrt_kerr_rk45_diag* diag;
+    bhrt_kerr_call c;
+    int* rejected; /* bhrt_kerr_rk45_diag's third plane or NULL */
     const bhrt_kerr_emit_params* ep;
-    const bhrt_kerr_emit_out* eo;
-    const bhrt_kerr_k* k;
+    bhrt_kerr_emit_out eo; /* NULL fields: not asked for */
 } emit_call;
+
+static const bhrt_kerr_emit_out k_no_emit_out = {NULL, NULL, NULL, NULL};
 
 /* the launch on `st` of context c (c NULL: the current device's, made here); device pointers */
 static int emit_body(devctx_t* c, hipStream_t st, const void* arg) {
@@ -131,35 +114,16 @@ static int emit_body(devctx_t* c, hipStream_t st, const void* arg) {
     if (!c) c = bhrt_ctx_get(bhrt_current_device());
     if (!c) return -1;
     bhrt_kparams kp;
-    /* the colour's constants and the sky map (the integration's are a->k) */
-    if (bhrt_fill_scene(&kp, a->bh, a->dk, a->cfg, INTEGRATOR_RK4, a->flags)) return -1;
     bhrt_kerr_emit_k ek;
     memset(&ek, 0, sizeof ek);
-    ek.rk.k = *a->k;
-    ek.rk.tol = a->cfg->tolerance;
+    if (bhrt_kerr_fill(&a->c, &kp, &ek.rk.k)) return -1;
+    ek.rk.tol = a->c.cfg->tolerance;
+    ek.rk.rejected = a->rejected;
     ek.max_crossings = a->ep->max_crossings;
     ek.q = a->ep->emissivity_index;
     ek.gain = a->ep->gain;
-    ek.spin_a = a->bh->spin * a->bh->mass;
-    if (a->eo) ek.out = *a->eo;
-    if (a->cam) {
-        bhrt_fill_camera(&kp, a->cam, a->W, a->H);
-        if (a->rows && a->rows->num_shards > 1) kp.cam.rows = *a->rows;
-        kp.n = a->nrows * a->W;
-        ek.rk.k.nrows = a->nrows;
-        ek.rk.k.tiles_x = (a->W + 7) / 8;
-        ek.rk.k.ntiles = ek.rk.k.tiles_x * ((a->nrows + 7) / 8);
-    } else {
-        kp.src = BHRT_SRC_RAYS;
-        kp.rays = a->d_rays;
-        kp.n = a->n;
-    }
-    kp.out = *a->out;
-    if (a->diag) {
-        ek.rk.k.h_residual = a->diag->h_residual;
-        ek.rk.k.lz_drift = a->diag->lz_drift;
-        ek.rk.rejected = a->diag->rejected;
-    }
+    ek.spin_a = a->c.bh->spin * a->c.bh->mass;
+    ek.out = a->eo;
     return bhrt_ctx_launch_fn(c, &kp, st, emit_fn, &ek);
 }
 
@@ -172,8 +136,10 @@ int bhrt_kerr_emit_frame_device(const BlackHoleParams* bh, const AccretionDiskPa
     int nrows = 0;
     if (emit_frame_check(bh, dk, cfg, cam, W, H, rows, flags, out, ep, eo, &k, &nrows)) return -1;
     if (nrows == 0) return 0;
-    const emit_call a = {bh,   dk,    cfg, cam,  W,  H,  nrows, rows,
-                         NULL, 0,     flags, out, diag, ep, eo,    &k};
+    const emit_call a = {{bh, dk, cfg, cam, W, H, nrows, rows, NULL, 0, flags, out,
+                          diag ? diag->h_residual : NULL,
+                              diag ? diag->lz_drift : NULL, &k},
+                         diag ? diag->rejected : NULL, ep, eo ? *eo : k_no_emit_out};
     return bhrt_on_stream(NULL, (hipStream_t)stream, emit_body, &a);
 }
 
@@ -184,82 +150,27 @@ int bhrt_kerr_emit_rays_device(const Ray* d_rays, int n, const BlackHoleParams* 
                                const bhrt_kerr_emit_out* eo, void* stream) {
     bhrt_kerr_k k;
     if (emit_rays_check(d_rays, n, bh, dk, cfg, flags, out, ep, eo, &k)) return -1;
-    const emit_call a = {bh,     dk, cfg,   NULL, 0,    0,  0,  NULL,
-                         d_rays, n,  flags, out,  diag, ep, eo, &k};
+    const emit_call a = {{bh, dk, cfg, NULL, 0, 0, 0, NULL, d_rays, n, flags, out,
+                          diag ? diag->h_residual : NULL,
+                              diag ? diag->lz_drift : NULL, &k},
+                         diag ? diag->rejected : NULL, ep, eo ? *eo : k_no_emit_out};
     return bhrt_on_stream(NULL, (hipStream_t)stream, emit_body, &a);
 }
 
-/* the host forms: `a` with host out / diag / emit and host rays (or a camera); n rays in all */
-static int emit_host(emit_call* a, const Ray* rays, long n) {
-    devctx_t* c = bhrt_ctx_get(bhrt_current_device());
-    if (!c || bhrt_ctx_streams(c)) return -1;
-    hipStream_t st = c->stream;
+/* the host forms: `a` with the host out and host rays (or a camera), n rays in all; the
+ * diagnostics and the emission's outputs are its seven planes. radius and redshift are written
+ * below a ray's count alone, so they start from the caller's values. */
+static int emit_host(emit_call* a, const bhrt_kerr_rk45_diag* diag, const bhrt_kerr_emit_out* eo,
+                     const Ray* rays, long n) {
     const size_t N = (size_t)n, K = (size_t)a->ep->max_crossings;
-    const bhrt_frame_soa* hout = a->out;
-    const bhrt_kerr_rk45_diag* hdiag = a->diag;
-    const bhrt_kerr_emit_out* heo = a->eo;
-    size_t bytes = bhrt_soa_bytes(hout, n) + 2 * align256(8 * N) + align256(4 * N) /* diag */
-                   + align256(4 * N) + 2 * align256(8 * K * N) + align256(8 * N); /* emit */
-    if (rays) bytes += align256(N * sizeof(Ray));
-    if (bhrt_ensure(&c->d_ss, &c->cap_ss, bytes, 0)) return -1;
-    char* p = (char*)c->d_ss;
-    if (rays) {
-        a->d_rays = (const Ray*)p;
-        HIP_TRY(hipMemcpyAsync(p, rays, N * sizeof(Ray), hipMemcpyHostToDevice, st));
-        p += align256(N * sizeof(Ray));
-    }
-    bhrt_frame_soa dout;
-    bhrt_soa_carve(&p, hout, n, &dout);
-    bhrt_kerr_rk45_diag ddiag = {NULL, NULL, NULL};
-    if (hdiag && hdiag->h_residual) ddiag.h_residual = (double*)p;
-    p += align256(8 * N);
-    if (hdiag && hdiag->lz_drift) ddiag.lz_drift = (double*)p;
-    p += align256(8 * N);
-    if (hdiag && hdiag->rejected) ddiag.rejected = (int*)p;
-    p += align256(4 * N);
-    bhrt_kerr_emit_out deo = {NULL, NULL, NULL, NULL};
-    if (heo && heo->count) deo.count = (int*)p;
-    p += align256(4 * N);
-    if (heo && heo->radius) deo.radius = (double*)p;
-    p += align256(8 * K * N);
-    if (heo && heo->redshift) deo.redshift = (double*)p;
-    p += align256(8 * K * N);
-    if (heo && heo->intensity) deo.intensity = (double*)p;
-    a->out = &dout;
-    a->diag = &ddiag;
-    a->eo = &deo;
-    /* sky_* are written for RAY_MAX_DISTANCE rays alone, radius and redshift below a ray's count
-     * alone: the other elements of the caller's arrays keep what they held, so the device planes
-     * start from the caller's values */
-    double* const hsky[3] = {hout->sky_x, hout->sky_y, hout->sky_z};
-    double* const dsky[3] = {dout.sky_x, dout.sky_y, dout.sky_z};
-    for (int f = 0; f < 3; f++)
-        if (hsky[f]) HIP_TRY(hipMemcpyAsync(dsky[f], hsky[f], 8 * N, hipMemcpyHostToDevice, st));
-    if (deo.radius)
-        HIP_TRY(hipMemcpyAsync(deo.radius, heo->radius, 8 * K * N, hipMemcpyHostToDevice, st));
-    if (deo.redshift)
-        HIP_TRY(hipMemcpyAsync(deo.redshift, heo->redshift, 8 * K * N, hipMemcpyHostToDevice, st));
-    if (emit_body(c, st, a)) return -1;
-    HIP_TRY(hipStreamSynchronize(st));
-    /* plain synchronous copies: caller memory is never page-locked */
-    void* const* hh = (void* const*)hout;
-    for (int f = 0; f < BHRT_NFIELDS; f++)
-        if (hh[f])
-            HIP_TRY(hipMemcpy(hh[f], ((void**)&dout)[f], k_fsize[f] * N, hipMemcpyDeviceToHost));
-    if (ddiag.h_residual)
-        HIP_TRY(hipMemcpy(hdiag->h_residual, ddiag.h_residual, 8 * N, hipMemcpyDeviceToHost));
-    if (ddiag.lz_drift)
-        HIP_TRY(hipMemcpy(hdiag->lz_drift, ddiag.lz_drift, 8 * N, hipMemcpyDeviceToHost));
-    if (ddiag.rejected)
-        HIP_TRY(hipMemcpy(hdiag->rejected, ddiag.rejected, 4 * N, hipMemcpyDeviceToHost));
-    if (deo.count) HIP_TRY(hipMemcpy(heo->count, deo.count, 4 * N, hipMemcpyDeviceToHost));
-    if (deo.radius)
-        HIP_TRY(hipMemcpy(heo->radius, deo.radius, 8 * K * N, hipMemcpyDeviceToHost));
-    if (deo.redshift)
-        HIP_TRY(hipMemcpy(heo->redshift, deo.redshift, 8 * K * N, hipMemcpyDeviceToHost));
-    if (deo.intensity)
-        HIP_TRY(hipMemcpy(heo->intensity, deo.intensity, 8 * N, hipMemcpyDeviceToHost));
-    return 0;
+    const bhrt_kerr_plane pl[] = {{diag ? diag->h_residual : NULL, &a->c.h_residual, 8 * N, 0},
+                                  {diag ? diag->lz_drift : NULL, &a->c.lz_drift, 8 * N, 0},
+                                  {diag ? diag->rejected : NULL, &a->rejected, 4 * N, 0},
+                                  {eo ? eo->count : NULL, &a->eo.count, 4 * N, 0},
+                                  {eo ? eo->radius : NULL, &a->eo.radius, 8 * K * N, 1},
+                                  {eo ? eo->redshift : NULL, &a->eo.redshift, 8 * K * N, 1},
+                                  {eo ? eo->intensity : NULL, &a->eo.intensity, 8 * N, 0}};
+    return bhrt_kerr_host(&a->c, rays, n, pl, 7, emit_body, a);
 }
 
 int bhrt_kerr_emit_frame(const BlackHoleParams* bh, const AccretionDiskParams* dk,
@@ -269,9 +180,9 @@ int bhrt_kerr_emit_frame(const BlackHoleParams* bh, const AccretionDiskParams* d
     bhrt_kerr_k k;
     int nrows = 0;
     if (emit_frame_check(bh, dk, cfg, cam, W, H, NULL, flags, out, ep, eo, &k, &nrows)) return -1;
-    emit_call a = {bh,   dk, cfg,   cam, W,    H,  nrows, NULL,
-                   NULL, 0,  flags, out, diag, ep, eo,    &k};
-    return emit_host(&a, NULL, (long)nrows * W);
+    emit_call a = {{bh, dk, cfg, cam, W, H, nrows, NULL, NULL, 0, flags, out, NULL, NULL, &k},
+                   NULL, ep, k_no_emit_out};
+    return emit_host(&a, diag, eo, NULL, (long)nrows * W);
 }
 
 int bhrt_kerr_emit_rays(const Ray* rays, int n, const BlackHoleParams* bh,
@@ -282,8 +193,9 @@ int bhrt_kerr_emit_rays(const Ray* rays, int n, const BlackHoleParams* bh,
     if (emit_rays_check(rays, n, bh, dk, cfg, flags, out, ep, eo, &k)) return -1;
     for (long i = 0; i < n; i++)
         if (bhrt_kerr_observer(&k, &rays[i].origin, i)) return -1;
-    emit_call a = {bh, dk, cfg, NULL, 0, 0, 0, NULL, NULL, n, flags, out, diag, ep, eo, &k};
-    return emit_host(&a, rays, n);
+    emit_call a = {{bh, dk, cfg, NULL, 0, 0, 0, NULL, NULL, n, flags, out, NULL, NULL, &k},
+                   NULL, ep, k_no_emit_out};
+    return emit_host(&a, diag, eo, rays, n);
 }
 
 int bhrt_kerr_disk_redshift(const BlackHoleParams* bh, double radius, double E, double lz,

@@ -98,8 +98,9 @@ static int kpaths_body(devctx_t* c, hipStream_t st, const void* arg) {
     if (bhrt_ctx_launch_fn(c, &kp, st, kpaths_fn, &pk)) return -1;
     /* The hit records are k_kerr's own, from its own launch behind the path launch: "what
      * bhrt_kerr_rays_device writes", bit for bit, colour and sky map included. The two kernels
-     * are two compilations of one step, so a path's last point and its hit_* agree to the
-     * contract's tolerance, not necessarily in every bit. bhrt_stats counts the two launches. */
+     * call one step and one set of tests (kerr.hip rk4_step, rk4_tests), each inlined into its own
+     * schedule, and the contract between a path's last point and its hit_* stays a tolerance, not
+     * every bit. bhrt_stats counts the two launches. */
     if (a->hits && bhrt_kerr_rays_on_device(c, st, a->d_rays, a->n, a->bh, a->dk, a->cfg, a->flags,
                                             a->hits, a->diag, a->k))
         return -1;
@@ -140,7 +141,11 @@ int bhrt_kerr_paths(const Ray* rays, int n, const BlackHoleParams* bh,
     size_t bytes = align256(N * sizeof(Ray)) + align256(N * sizeof(int32_t));
     if (paths->xyz) bytes += align256(N * P * sizeof(Vector3D));
     if (paths->xyz32) bytes += align256(N * P * 3 * sizeof(float));
-    if (hits) bytes += bhrt_soa_bytes(hits, n) + 2 * align256(8 * N);
+    /* (kerr.c's staging pieces for the hit records; the diagnostics are their two planes) */
+    bhrt_kerr_diag ddiag = {NULL, NULL};
+    const bhrt_kerr_plane pl[] = {{diag ? diag->h_residual : NULL, &ddiag.h_residual, 8 * N, 0},
+                                  {diag ? diag->lz_drift : NULL, &ddiag.lz_drift, 8 * N, 0}};
+    if (hits) bytes += bhrt_kerr_stage_bytes(hits, n, pl, 2);
     if (bhrt_ensure(&c->d_ss, &c->cap_ss, bytes, 0)) return -1;
     char* p = (char*)c->d_ss;
     Ray* d_rays = (Ray*)p;
@@ -158,21 +163,8 @@ int bhrt_kerr_paths(const Ray* rays, int n, const BlackHoleParams* bh,
         p += align256(N * P * 3 * sizeof(float));
     }
     bhrt_frame_soa dhits;
-    bhrt_kerr_diag ddiag = {NULL, NULL};
     HIP_TRY(hipMemcpyAsync(d_rays, rays, N * sizeof(Ray), hipMemcpyHostToDevice, st));
-    if (hits) {
-        bhrt_soa_carve(&p, hits, n, &dhits);
-        if (diag && diag->h_residual) ddiag.h_residual = (double*)p;
-        p += align256(8 * N);
-        if (diag && diag->lz_drift) ddiag.lz_drift = (double*)p;
-        /* sky_* are written for RAY_MAX_DISTANCE rays alone: the other elements of the caller's
-         * arrays keep what they held, so the device planes start from the caller's values */
-        double* const hsky[3] = {hits->sky_x, hits->sky_y, hits->sky_z};
-        double* const dsky[3] = {dhits.sky_x, dhits.sky_y, dhits.sky_z};
-        for (int f = 0; f < 3; f++)
-            if (hsky[f])
-                HIP_TRY(hipMemcpyAsync(dsky[f], hsky[f], 8 * N, hipMemcpyHostToDevice, st));
-    }
+    if (hits && bhrt_kerr_stage_carve(&p, st, hits, n, &dhits, pl, 2)) return -1;
     const kpaths_call a = {d_rays, n, bh, dk, cfg, max_positions, every, flags, &dev,
                            hits ? &dhits : NULL, diag ? &ddiag : NULL, &k};
     if (kpaths_body(c, st, &a)) return -1;
@@ -198,16 +190,6 @@ int bhrt_kerr_paths(const Ray* rays, int n, const BlackHoleParams* bh,
         rc = bhrt_rows_back(paths->xyz32, dev.xyz32, count, n, P, 3 * sizeof(float));
     free(own_count);
     if (rc) return -1;
-    if (hits) {
-        void* const* hh = (void* const*)hits;
-        for (int f = 0; f < BHRT_NFIELDS; f++)
-            if (hh[f])
-                HIP_TRY(hipMemcpy(hh[f], ((void**)&dhits)[f], k_fsize[f] * N,
-                                  hipMemcpyDeviceToHost));
-        if (ddiag.h_residual)
-            HIP_TRY(hipMemcpy(diag->h_residual, ddiag.h_residual, 8 * N, hipMemcpyDeviceToHost));
-        if (ddiag.lz_drift)
-            HIP_TRY(hipMemcpy(diag->lz_drift, ddiag.lz_drift, 8 * N, hipMemcpyDeviceToHost));
-    }
+    if (hits && bhrt_kerr_stage_back(hits, n, &dhits, pl, 2)) return -1;
     return 0;
 }

@@ -13,7 +13,15 @@ taken out: comments, the function index of block labels (.LBB<n>_<k> -> .LBB_<k>
 labels (.Ltmp<n>, renumbered per function by first appearance), .Lfunc_begin / .Lfunc_end, and
 the compilation-unit id (__hip_cuid_<id> and every other occurrence of <id>).
 Prints the counts and every difference; exit status 0 only if there is none.
+
+    tools/isa_identity.py --counts A.s [B.s]
+
+For each kernel of each file: the number of instructions and the count of every FP64 vector
+mnemonic (v_*_f64). With two files, the differences of B from A as well; exit status 0 only if
+every kernel of A has the same FP64 counts in B. A register renumbering or another schedule keeps
+these counts; another contraction or another order of the arithmetic does not.
 """
+import collections
 import re
 import sys
 
@@ -66,7 +74,36 @@ def normalise(body):
     return out
 
 
+def counts(paths):
+    per_file = []
+    for path in paths:
+        funcs, descs = parse(path)
+        table = {}
+        for name in sorted(descs):
+            ops = [ln.split()[0] for ln in funcs[name] if not re.match(r"^[.\w$]+:$|^\.", ln)]
+            table[name] = (len(ops), collections.Counter(
+                op for op in ops if op.startswith("v_") and op.endswith("_f64")))
+            print("%s %s: %d instructions" % (path, name, len(ops)))
+            for op, n in sorted(table[name][1].items()):
+                print("  %-24s %5d" % (op, n))
+        per_file.append(table)
+    if len(per_file) < 2:
+        return 0
+    a, b = per_file
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        (ta, ca), (tb, cb) = a.get(name, (0, {})), b.get(name, (0, {}))
+        diff = {op: cb.get(op, 0) - ca.get(op, 0) for op in set(ca) | set(cb)
+                if ca.get(op, 0) != cb.get(op, 0)}
+        print("%s: instructions %d -> %d (%+d), FP64 counts %s" %
+              (name, ta, tb, tb - ta, "EQUAL" if not diff else "DIFFER %s" % sorted(diff.items())))
+        bad += bool(diff)
+    return 1 if bad else 0
+
+
 def main():
+    if len(sys.argv) in (3, 4) and sys.argv[1] == "--counts":
+        return counts(sys.argv[2:])
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     pf, pd = parse(sys.argv[1])
