@@ -1204,6 +1204,105 @@ int bhrt_kerr_emit_rays(const Ray* rays, int n, const BlackHoleParams* blackhole
 int bhrt_kerr_disk_redshift(const BlackHoleParams* blackhole, double radius, double E, double lz,
                             double* g);
 
+/* ---- Physical particles: timelike geodesics for resident systems ----
+ * bhrt_particles_update_device reproduces the reference's update_particles operation for
+ * operation: an Euler step on a four-entry subset of the Christoffel symbols for a test particle
+ * inside 20 rs, Newtonian gravity for every other. No orbit of it is stable, nothing knows the ISCO
+ * and nothing plunges. bhrt_particles_kerr_update_device advances the same resident object along
+ * true timelike geodesics of Kerr in coordinate time instead: an opt-in update with its own kernel,
+ * beside the parity update; every call above keeps its bits.
+ *
+ * THE PARTICLE RULE (tests/kerr_particles_rule.py restates it in numpy). All arithmetic is IEEE
+ * double.
+ *  Spin.       a = +(spin * mass), not a~: particles run forward in time, so there is no time
+ *              reversal. Geometry, Hamiltonian and Equations are THE RULE's of "Physical geodesics"
+ *              with a~ replaced by a. With this sign the disk's prograde circular orbits (about +z
+ *              in +phi, bhrt_kerr_orbit_velocity) are circular; with the other they plunge.
+ *  State.      position is Kerr-Schild Cartesian; velocity is the coordinate velocity dx/dt against
+ *              Kerr-Schild time t, which is what a tick advances: all particles of a system stay on
+ *              one time slice.
+ *  From velocity to momentum, at the start of every call, per active particle, with f and l at x
+ *              and unit rest mass (Particle.mass is not read): w = 1 + l.v,
+ *              N = (1 - v.v) - f w^2; the particle is timelike iff N is finite and > 0;
+ *              u^t = 1 / sqrt(N), p = u^t (v + f w l), E = u^t (1 - f w), L_z = x p_y - y p_x.
+ *              H = -1/2 holds by construction.
+ *  Equations.  xdot and pdot as for the rays; tdot = E + f u with u = E + l.p. Integrated against
+ *              t: d(x, p)/dt = (xdot, pdot) / tdot and dtau/dt = 1 / tdot, seven components, the
+ *              reciprocal of tdot formed once per stage.
+ *  Tick.       One tick advances t by dt = config->time_step. With r at the tick's start,
+ *              m = substeps ceil(1 / min(1, max(r / (8 M), 1 / 16))) -- the ray rule's step schedule
+ *              as an integer count -- and h = dt / m. A tick is m classical RK4 steps of size h on
+ *              the seven components, with the ray rule's weights and summation order. A tick that
+ *              begins adds dt to age and to coordinate_time.
+ *  After each substep, in this order:
+ *              1. any non-finite component: the particle keeps the state it had before that
+ *                 substep, active = 0, status ERROR, and the call is over for it;
+ *              2. r_new <= r+ = M + sqrt(M^2 - a^2): captured, active = 0, status CAPTURED, the
+ *                 position is that point, and the call is over for it. Ingoing Kerr-Schild
+ *                 coordinates are regular on the horizon: a plunging particle arrives there with
+ *                 finite fields.
+ *  At the call's start, nothing else being written in each case: a particle with active == 0 is
+ *              not touched, in any byte; an active particle with r <= r+ is captured, active = 0 and
+ *              status CAPTURED (decided first, whatever its velocity); an active particle that is
+ *              not timelike gets status NOT_TIMELIKE, is not touched and stays active.
+ *  Written at the end, for a particle that ran: position; velocity = xdot / tdot at the last point;
+ *              energy = E; angular_momentum = x p_y - y p_x at the last point; proper_time += the
+ *              tau integrated in this call; coordinate_time; age; time_dilation = tdot at the last
+ *              point (dt/dtau, >= 1 far away); active. acceleration, mass, type, id and temperature
+ *              keep their bytes. Every ParticleType moves by the same rule.
+ *  Block counts. The launch leaves the object's per-256-particle active counts as the parity
+ *              update leaves them, counted after the update: bhrt_particles_extract* works
+ *              unchanged after either kind of update. updates advances by one per call, AT THE CALL.
+ *  Composition. E is formed again from velocity at every call: two calls of s ticks agree with one
+ *              call of 2 s ticks to rounding in position and velocity, NOT IN BITS; energy,
+ *              angular_momentum, time_dilation and the later proper_time agree to half the
+ *              |2H + 1| that the integrator left on the state carried up to the split.
+ *  Determinism. No atomic touches an output: a particle's result is a pure function of its own
+ *              fields and the scene, the same bits run to run, on any stream, whatever the count
+ *              and wherever the particle stands in the array.
+ *  Diagnostics (bhrt_kerr_particles_diag, optional DEVICE arrays [count] by array index; every
+ *              element of a given array is written): h_residual, the largest
+ *              |((p.p - E^2) - f u^2) + 1| / (((E^2 + p.p) + f u^2) + 1) over the start point and
+ *              every finite substep end; lz_drift, |L_z,end - L_z,0|; status (int), one of
+ *              BHRT_PSTAT_*; substeps (int), the RK4 substeps taken in this call. Particles that did
+ *              not run get zeros in h_residual, lz_drift and substeps.
+ *  Refusals.   -1 with bhrt_last_error set, nothing written, no state changed and updates
+ *              unchanged, each decided BEFORE ANY HIP CALL (the current device's query aside):
+ *              everything bhrt_particles_update_device refuses -- a NULL object, blackhole or
+ *              config, steps < 0, a current device other than the object's --; |spin| >= 1 or NaN;
+ *              mass not finite or not > 0; time_step not finite or not > 0; a NULL params; substeps
+ *              outside 1..64. steps == 0 is a no-op that returns 0. HIP failures also return -1.
+ *  Streams.    As for bhrt_particles_update_device: asynchronous, NO host wait; NULL is ordered like
+ *              the legacy default stream; the caller orders calls on one object.
+ *  Not offered. Massless or charged particles; an adaptive (Dormand-Prince) particle step; a host
+ *              one-shot on a ParticleSystem (a caller composes create, update and download);
+ *              particle-disk interaction; bhrt_stats entries (the parity update has none either). */
+#define BHRT_PSTAT_MOVED 0
+#define BHRT_PSTAT_CAPTURED 1
+#define BHRT_PSTAT_NOT_TIMELIKE 2
+#define BHRT_PSTAT_ERROR 3
+#define BHRT_PSTAT_INACTIVE 4
+typedef struct { int substeps; } bhrt_kerr_particles_params;
+typedef struct { double* h_residual; double* lz_drift; int* status; int* substeps; } bhrt_kerr_particles_diag;
+
+int bhrt_particles_kerr_update_device(bhrt_particles* ps, const BlackHoleParams* blackhole,
+                                      const SimulationConfig* config, int steps,
+                                      const bhrt_kerr_particles_params* params,
+                                      const bhrt_kerr_particles_diag* device_diag /* may be NULL */,
+                                      void* hip_stream);
+/* The velocity-to-momentum paragraph on the host with the device's operations: state = (x, p), *E,
+ * *ut. 0; 1 and nothing written if not timelike or r <= r+; -1 for a NULL argument or a bad
+ * blackhole as above. No HIP call. */
+int bhrt_kerr_particle_state(const BlackHoleParams* blackhole, const Vector3D* position,
+                             const Vector3D* velocity, double state[6], double* E, double* ut);
+/* Orbit helper: the coordinate velocity of the circular equatorial geodesic through `position` (z
+ * must be 0): r = sqrt(x^2 + y^2 - a^2), Omega = +-sqrt(M) / (r sqrt(r) +- a sqrt(M)) (upper sign:
+ * prograde, about +z in +phi, the emission rule's Omega), v = Omega (-y, x, 0). 0; 1 and nothing
+ * written where no timelike circular orbit exists (r <= r+, or r sqrt(r) - 3 M sqrt(r) +-
+ * 2 a sqrt(M) <= 0); -1 for a NULL argument, z != 0 or a bad blackhole. No HIP call. */
+int bhrt_kerr_orbit_velocity(const BlackHoleParams* blackhole, const Vector3D* position, int prograde,
+                             Vector3D* velocity);
+
 /* Last error message of the calling thread ("" if none). */
 const char* bhrt_last_error(void);
 

@@ -270,6 +270,29 @@ class KerrEmitOut(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in EMIT_FIELDS]
 
 
+# BHRT_PSTAT_*: what bhrt_particles_kerr_update_device did with a particle
+PSTAT_MOVED, PSTAT_CAPTURED, PSTAT_NOT_TIMELIKE, PSTAT_ERROR, PSTAT_INACTIVE = 0, 1, 2, 3, 4
+KERR_PARTICLES_MAX_SUBSTEPS = 64
+
+
+class KerrParticlesParams(C.Structure):
+    """bhrt_kerr_particles_params: substeps (1..64), the RK4 substeps of a tick far from the hole."""
+    _fields_ = [("substeps", C.c_int)]
+
+    def __init__(self, substeps=1):
+        super().__init__(substeps)
+
+
+KERR_PARTICLES_DIAG_FIELDS = ("h_residual", "lz_drift", "status", "substeps")
+KERR_PARTICLES_DIAG_DTYPES = {"h_residual": np.float64, "lz_drift": np.float64,
+                              "status": np.int32, "substeps": np.int32}
+
+
+class KerrParticlesDiag(C.Structure):
+    """bhrt_kerr_particles_diag: optional DEVICE arrays [count] by array index; 0 = not produced."""
+    _fields_ = [(f, C.c_void_p) for f in KERR_PARTICLES_DIAG_FIELDS]
+
+
 class ParticlesState(C.Structure):
     """bhrt_particles_state: the host-side state of a device-resident particle system."""
     _fields_ = [("count", C.c_int32), ("device", C.c_int32), ("updates", C.c_int64)]

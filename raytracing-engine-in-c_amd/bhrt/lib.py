@@ -179,6 +179,15 @@ _PROTOS = {
                                   _P(abi.KerrDiag)]),
     "bhrt_kerr_ray_init": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.Vector3D), _P(abi.Vector3D),
                                      _P(C.c_double * 6), _P(C.c_double)]),
+    "bhrt_particles_kerr_update_device": (C.c_int, [C.c_void_p, _P(abi.BlackHoleParams),
+                                                    _P(abi.SimulationConfig), C.c_int,
+                                                    _P(abi.KerrParticlesParams),
+                                                    _P(abi.KerrParticlesDiag), C.c_void_p]),
+    "bhrt_kerr_particle_state": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.Vector3D),
+                                           _P(abi.Vector3D), _P(C.c_double * 6), _P(C.c_double),
+                                           _P(C.c_double)]),
+    "bhrt_kerr_orbit_velocity": (C.c_int, [_P(abi.BlackHoleParams), _P(abi.Vector3D), C.c_int,
+                                           _P(abi.Vector3D)]),
     "bhrt_trace_rays": (C.c_int, [C.c_void_p, C.c_int, _P(abi.BlackHoleParams),
                                   _P(abi.AccretionDiskParams), _P(abi.SimulationConfig), C.c_int,
                                   C.c_int, _P(abi.FrameSoA)]),
@@ -860,6 +869,45 @@ def kerr_ray_init(bh, origin, direction):
     _check(load().bhrt_kerr_ray_init(_ptr(bh), C.byref(o), C.byref(d), C.byref(state), C.byref(E)),
            "bhrt_kerr_ray_init")
     return np.array(state[:]), E.value
+
+
+def particles_kerr_update_device(ps, bh, cfg, steps=1, params=None, diag=None, stream=None):
+    """bhrt_particles_kerr_update_device: `steps` ticks of the resident array along timelike Kerr
+    geodesics (abi.KerrParticlesParams; None: substeps 1), the diagnostics into the device arrays
+    of `diag` (abi.KerrParticlesDiag or None), asynchronous on a hipStream_t (int handle or
+    None)."""
+    if params is None:
+        params = abi.KerrParticlesParams()
+    _check(load().bhrt_particles_kerr_update_device(ps, _ptr(bh), _ptr(cfg), int(steps),
+                                                    _ptr(params), _ptr(diag),
+                                                    C.c_void_p(stream) if stream else None),
+           "bhrt_particles_kerr_update_device")
+
+
+def kerr_particle_state(bh, position, velocity):
+    """bhrt_kerr_particle_state: (state [6] = (x, p), E, u^t) of a unit-mass particle with
+    coordinate velocity `velocity` at `position`, on the host; None where it is not timelike or
+    lies inside the horizon."""
+    state = (C.c_double * 6)()
+    E, ut = C.c_double(), C.c_double()
+    x, v = abi.v3(*position), abi.v3(*velocity)
+    rc = load().bhrt_kerr_particle_state(_ptr(bh), C.byref(x), C.byref(v), C.byref(state),
+                                         C.byref(E), C.byref(ut))
+    if rc == 1:
+        return None
+    _check(rc, "bhrt_kerr_particle_state")
+    return np.array(state[:]), E.value, ut.value
+
+
+def kerr_orbit_velocity(bh, position, prograde=True):
+    """bhrt_kerr_orbit_velocity: the coordinate velocity [3] of the circular equatorial geodesic
+    through `position` (z == 0); None where no timelike circular orbit exists."""
+    x, v = abi.v3(*position), abi.Vector3D()
+    rc = load().bhrt_kerr_orbit_velocity(_ptr(bh), C.byref(x), 1 if prograde else 0, C.byref(v))
+    if rc == 1:
+        return None
+    _check(rc, "bhrt_kerr_orbit_velocity")
+    return np.array([v.x, v.y, v.z])
 
 
 def set_claim_order(d_order_ptr, n):

@@ -9,7 +9,7 @@
  *   batch.c        trace_ray / trace_rays_batch: the pipelined chunks
  *   dropin.c       integrate_photon_path, trace_pixel, the bh_* context API
  *   supersample.c, adaptive.c, temporal.c, paths.c, particles.c, particles_resident.c, sky.c,
- *   kerr.c, kerr_paths.c, kerr_rk45.c, kerr_emit.c
+ *   kerr.c, kerr_paths.c, kerr_rk45.c, kerr_emit.c, kerr_particles.c
  *                  features with launchers of their own
  */
 #ifndef BHRT_HOST_H

@@ -391,6 +391,24 @@ typedef struct {
 int bhrt_launch_kerr_emit(const bhrt_kparams* kp, const bhrt_kerr_emit_k* ek, void* stream,
                           void* ev0, void* ev1);
 
+/* Physical particles (kerr_particles.c; kerr.hip k_kerr_particles; the rule: include/bhrt_api.h
+ * "Physical particles"). k holds the constants bhrt_launch_kerr gets for the same scene with
+ * a = +(spin * mass) -- particles run forward in time --; of it M, two_m, a, a2, r_plus, eight_m
+ * and dt are read, and h_residual / lz_drift are bhrt_kerr_particles_diag's planes. */
+typedef struct {
+    bhrt_kerr_k k;
+    int substeps;         /* params->substeps, checked: 1..64                                 */
+    int* status;          /* bhrt_kerr_particles_diag.status, device [count] or NULL          */
+    int* substeps_out;    /* bhrt_kerr_particles_diag.substeps, device [count] or NULL        */
+} bhrt_kerr_particles_k;
+
+/* kerr.hip: `steps` ticks of d_particles[0, count) in 256-lane workgroups, and d_block_active[b] =
+ * workgroup b's particles active after them, as bhrt_launch_particles_counted leaves it;
+ * asynchronous on `stream`, ev0/ev1 (hipEvent_t, may be NULL) recorded around the kernel; 0 or a
+ * hipError_t value */
+int bhrt_launch_kerr_particles(Particle* d, int count, const bhrt_kerr_particles_k* k, int steps,
+                               int* d_block_active, void* stream, void* ev0, void* ev1);
+
 /* launch helpers implemented in geodesic.hip; return 0 or a hipError_t value.
  * bhrt_launch_trace records ev0/ev1 (hipEvent_t, may be NULL) around the trace kernel
  * itself, not the set-up or colour passes. */

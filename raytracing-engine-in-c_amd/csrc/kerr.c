@@ -343,3 +343,59 @@ int bhrt_kerr_ray_init(const BlackHoleParams* bh, const Vector3D* origin, const 
     state[5] = p[2];
     return 0;
 }
+
+/* the scene's constants with the particle rule's spin a = +(spin * mass), or -1 */
+static int particle_scene(const BlackHoleParams* bh, bhrt_kerr_k* k) {
+    const SimulationConfig cfg = {.time_step = 1.0};
+    if (bhrt_kerr_scene(bh, NULL, &cfg, k)) return -1;
+    k->a = bh->spin * bh->mass;
+    return 0;
+}
+
+int bhrt_kerr_particle_state(const BlackHoleParams* bh, const Vector3D* position,
+                             const Vector3D* velocity, double state[6], double* E, double* ut) {
+    if (!bh || !position || !velocity || !state || !E || !ut) {
+        bhrt_set_err("kerr particles: NULL argument");
+        return -1;
+    }
+    bhrt_kerr_k k;
+    if (particle_scene(bh, &k)) return -1;
+    const double v[3] = {velocity->x, velocity->y, velocity->z};
+    double f, l[3], p[3], e, u;
+    const double r = bhrt_kerr_fields(position->x, position->y, position->z, k.a, k.a2, k.two_m,
+                                      &f, l);
+    if (r <= k.r_plus || !bhrt_kerr_particle(f, l, v, p, &e, &u)) return 1;
+    state[0] = position->x;
+    state[1] = position->y;
+    state[2] = position->z;
+    state[3] = p[0];
+    state[4] = p[1];
+    state[5] = p[2];
+    *E = e;
+    *ut = u;
+    return 0;
+}
+
+int bhrt_kerr_orbit_velocity(const BlackHoleParams* bh, const Vector3D* position, int prograde,
+                             Vector3D* velocity) {
+    if (!bh || !position || !velocity) {
+        bhrt_set_err("kerr particles: NULL argument");
+        return -1;
+    }
+    bhrt_kerr_k k;
+    if (particle_scene(bh, &k)) return -1;
+    if (!(position->z == 0.0)) {
+        bhrt_set_err("kerr particles: an equatorial orbit needs z == 0 (z = %g)", position->z);
+        return -1;
+    }
+    const double x = position->x, y = position->y;
+    const double s = prograde ? 1.0 : -1.0;
+    const double r = sqrt((x * x + y * y) - k.a2);
+    const double sm = sqrt(k.M), sr = sqrt(r);
+    if (!(r > k.r_plus) || !((r * sr - 3.0 * k.M * sr) + s * (2.0 * k.a * sm) > 0.0)) return 1;
+    const double omega = s * sm / (r * sr + s * (k.a * sm));
+    velocity->x = omega * -y;
+    velocity->y = omega * x;
+    velocity->z = 0.0;
+    return 0;
+}

@@ -1,5 +1,5 @@
-// kerr.hip -- physical null geodesics of Kerr in Cartesian Kerr-Schild coordinates: four kernels
-// and their launchers.
+// kerr.hip -- physical geodesics of Kerr in Cartesian Kerr-Schild coordinates: four kernels for
+// null rays and one for timelike particles, and their launchers.
 //   k_kerr        fixed-step RK4 rays            rule: include/bhrt_api.h "Physical geodesics",
 //                                                tests/kerr_rule.py; host side kerr.c
 //   k_kerr_paths  the same rays' polylines       "Physical photon paths", tests/kerr_paths_rule.py;
@@ -8,6 +8,9 @@
 //                                                tests/kerr_rk45_rule.py; kerr_rk45.c
 //   k_kerr_emit   adaptive rays with recorded    "Kerr disk emission", tests/kerr_emit_rule.py;
 //                 disk crossings                 kerr_emit.c
+//   k_kerr_particles  a resident particle        "Physical particles", tests/kerr_particles_rule.py;
+//                 system along timelike          kerr_particles.c. One lane per particle in 256-lane
+//                 geodesics                      workgroups, on the same geom and deriv (at the end)
 //
 // One lane per ray, FP64. A wavefront claims 64 rays at a time from the launch's claim counter --
 // an 8x8 pixel tile of a camera frame, so that its rays live alike, or 64 consecutive rays of an
@@ -1020,6 +1023,161 @@ __global__ __launch_bounds__(64, kEmitWaves) void k_kerr_emit(const bhrt_kparams
     wave_stats(kp.ctl, lane, n_rays, n_steps);
 }
 
+// ---- timelike geodesics of resident particle systems: k_kerr_particles --------------------------
+
+// One stage of the particle rule at s = (x, p, tau) with geometry g: d(x, p)/dt = (xdot, pdot) /
+// tdot and dtau/dt = 1 / tdot with tdot = E + f u, its reciprocal formed once. Returns tdot.
+__device__ __forceinline__ double particle_stage(const Geom& g, const double (&s)[7], double E,
+                                                 const bhrt_kerr_k& k, double (&d)[7]) {
+    double xp[6];
+    deriv(g, s[0], s[1], s[2], s[3], s[4], s[5], E, k, xp);
+    const double u = E + ((g.lx * s[3] + g.ly * s[4]) + g.lz * s[5]);
+    const double tdot = E + g.f * u;
+    const double it = 1.0 / tdot;
+#pragma unroll
+    for (int c = 0; c < 6; c++) d[c] = xp[c] * it;
+    d[6] = it;
+    return tdot;
+}
+
+__device__ __forceinline__ double particle_stage_at(const double (&s)[7], double E,
+                                                    const bhrt_kerr_k& k, double (&d)[7]) {
+    return particle_stage(geom(s[0], s[1], s[2], k), s, E, k, d);
+}
+
+// |((p.p - E^2) - f u^2) + 1| / (((E^2 + p.p) + f u^2) + 1): 2H + 1 of a unit-mass particle
+__device__ __forceinline__ double particle_residual(const Geom& g, const double (&y)[7],
+                                                    double E) {
+    const double u = E + ((g.lx * y[3] + g.ly * y[4]) + g.lz * y[5]);
+    const double pp = (y[3] * y[3] + y[4] * y[4]) + y[5] * y[5];
+    const double fu2 = g.f * (u * u);
+    return fabs(((pp - E * E) - fu2) + 1.0) / (((E * E + pp) + fu2) + 1.0);
+}
+
+// particles.hip's block_count, which the resident object's extract relies on: the workgroup's
+// count of set flags into block_active[blockIdx.x]. Every lane of the workgroup calls it.
+__device__ __forceinline__ void particles_block_count(bool active, int* block_active) {
+    __shared__ int wave_count[4];
+    const unsigned long long m = __ballot(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        block_active[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+}
+
+// THE PARTICLE RULE for particle i: loaded once, `steps` ticks in registers, stored once if it
+// ran; returns its active flag after the call. Lanes of a wave take different numbers of substeps
+// per tick (1 to 16 times pk.substeps) and wait for the longest: one flat loop over substeps, a
+// tick begun where a lane's count runs out, so that lanes in different ticks still step together.
+__device__ __forceinline__ int kerr_particle(Particle* ps, int i, const bhrt_kerr_particles_k& pk,
+                                             int steps) {
+    const bhrt_kerr_k& kk = pk.k;
+    const bool diag = kk.h_residual != nullptr;
+    Particle p = ps[i];
+    int status = BHRT_PSTAT_INACTIVE, nsub = 0;
+    double hres = 0.0, lzd = 0.0;
+    if (p.active) {
+        double f0, l0[3], p0[3], E, ut;
+        const double v0[3] = {p.velocity.x, p.velocity.y, p.velocity.z};
+        const double r0 = bhrt_kerr_fields(p.position.x, p.position.y, p.position.z, kk.a, kk.a2,
+                                           kk.two_m, &f0, l0);
+        if (r0 <= kk.r_plus) {  // inside the horizon at the start: the flag alone is written
+            status = BHRT_PSTAT_CAPTURED;
+            p.active = 0;
+            ps[i].active = 0;
+        } else if (!bhrt_kerr_particle(f0, l0, v0, p0, &E, &ut)) {
+            status = BHRT_PSTAT_NOT_TIMELIKE;
+        } else {
+            status = BHRT_PSTAT_MOVED;
+            double y[7] = {p.position.x, p.position.y, p.position.z, p0[0], p0[1], p0[2], 0.0};
+            Geom g = geom(y[0], y[1], y[2], kk);
+            const double lz0 = y[0] * y[4] - y[1] * y[3];
+            if (diag) hres = particle_residual(g, y, E);
+            int tick = 0, left = 0;
+            double h = 0.0;
+            for (;;) {
+                if (left == 0) {  // a tick begins: m substeps of dt / m, m from r here
+                    if (tick == steps) break;
+                    tick++;
+                    const double q = fmin(1.0, fmax(g.r / kk.eight_m, 0.0625));
+                    left = pk.substeps * (int)ceil(1.0 / q);
+                    h = kk.dt / (double)left;
+                    p.age += kk.dt;
+                    p.coordinate_time += kk.dt;
+                }
+                const double hh = 0.5 * h;
+                double k1[7], k2[7], k3[7], k4[7], s[7], yn[7];
+                (void)particle_stage(g, y, E, kk, k1);
+#pragma unroll
+                for (int c = 0; c < 7; c++) s[c] = y[c] + hh * k1[c];
+                (void)particle_stage_at(s, E, kk, k2);
+#pragma unroll
+                for (int c = 0; c < 7; c++) s[c] = y[c] + hh * k2[c];
+                (void)particle_stage_at(s, E, kk, k3);
+#pragma unroll
+                for (int c = 0; c < 7; c++) s[c] = y[c] + h * k3[c];
+                (void)particle_stage_at(s, E, kk, k4);
+                const double h6 = h / 6.0;
+#pragma unroll
+                for (int c = 0; c < 7; c++)
+                    yn[c] = y[c] + h6 * ((k1[c] + 2.0 * k2[c]) + (2.0 * k3[c] + k4[c]));
+                nsub++;
+                left--;
+                bool finite = true;
+#pragma unroll
+                for (int c = 0; c < 7; c++) finite = finite && fabs(yn[c]) <= kDblMax;
+                if (!finite) {  // 1. the state before this substep stays
+                    status = BHRT_PSTAT_ERROR;
+                    p.active = 0;
+                    break;
+                }
+                g = geom(yn[0], yn[1], yn[2], kk);
+#pragma unroll
+                for (int c = 0; c < 7; c++) y[c] = yn[c];
+                if (diag) hres = fmax(hres, particle_residual(g, y, E));
+                if (g.r <= kk.r_plus) {  // 2. captured at that point
+                    status = BHRT_PSTAT_CAPTURED;
+                    p.active = 0;
+                    break;
+                }
+            }
+            double d[7];
+            const double tdot = particle_stage(g, y, E, kk, d);
+            const double lz = y[0] * y[4] - y[1] * y[3];
+            lzd = fabs(lz - lz0);
+            p.position.x = y[0];
+            p.position.y = y[1];
+            p.position.z = y[2];
+            p.velocity.x = d[0];
+            p.velocity.y = d[1];
+            p.velocity.z = d[2];
+            p.energy = E;
+            p.angular_momentum = lz;
+            p.proper_time += y[6];
+            p.time_dilation = tdot;
+            ps[i] = p;
+        }
+    }
+    if (kk.h_residual) kk.h_residual[i] = hres;
+    if (kk.lz_drift) kk.lz_drift[i] = lzd;
+    if (pk.status) pk.status[i] = status;
+    if (pk.substeps_out) pk.substeps_out[i] = nsub;
+    return p.active;
+}
+
+// One lane per particle in 256-lane workgroups, the particle index blockIdx.x * 256 + threadIdx.x:
+// the layout of the resident object's per-workgroup active counts (particles.hip), which this
+// kernel leaves as the parity update's counting kernel does. Lanes past count add 0 and stay for
+// the barrier. FP64, no atomic.
+__global__ __launch_bounds__(256) void k_kerr_particles(Particle* ps, int count,
+                                                        const bhrt_kerr_particles_k pk, int steps,
+                                                        int* block_active) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int active = 0;
+    if (i < count) active = kerr_particle(ps, i, pk, steps);
+    particles_block_count(active != 0, block_active);
+}
+
 // One launch: as many one-wave workgroups as are resident at once (bhrt_launch.h), at most one
 // per unit, with ev0 / ev1 recorded around the kernel; 0 or a hipError_t value.
 template <auto KERNEL, class Arg>
@@ -1037,6 +1195,18 @@ int launch(const bhrt_kparams* kp, const Arg* arg, long units, void* stream, voi
 }
 
 }  // namespace
+
+extern "C" int bhrt_launch_kerr_particles(Particle* d, int count, const bhrt_kerr_particles_k* k,
+                                          int steps, int* d_block_active, void* stream, void* ev0,
+                                          void* ev1) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ev0) (void)hipEventRecord(static_cast<hipEvent_t>(ev0), st);
+    if (count > 0 && steps > 0)
+        k_kerr_particles<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(d, count, *k, steps,
+                                                                         d_block_active);
+    if (ev1) (void)hipEventRecord(static_cast<hipEvent_t>(ev1), st);
+    return (int)hipGetLastError();
+}
 
 extern "C" int bhrt_launch_kerr_emit(const bhrt_kparams* kp, const bhrt_kerr_emit_k* ek,
                                      void* stream, void* ev0, void* ev1) {

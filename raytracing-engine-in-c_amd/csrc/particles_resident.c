@@ -22,23 +22,7 @@
 #include <string.h>
 
 #include "bhrt_host.h"
-
-struct bhrt_particles {
-    int device, count;
-    int64_t updates;
-    Particle* d_buf;      /* the resident array */
-    size_t cap;           /* particles */
-    int* d_blocks;        /* block_active [cap_blocks], then offsets [cap_blocks + 1] */
-    size_t cap_blocks;
-    void* d_out;          /* bhrt_particles_extract: device outputs of the host form */
-    size_t cap_out;
-    void* h_out;          /* ... and their pinned staging */
-    size_t cap_hout;
-    hipEvent_t ev[10];    /* bhrt_particles_kernel_ms */
-    int have_ev;
-    hipStream_t last;     /* the stream of the last update or device extract */
-    int used;
-};
+#include "particles_resident.h" /* the object, check_object, check_device, used_on */
 
 #define BHRT_PARTICLES_ONE_COPY ((size_t)1 << 20) /* bytes: the host extract's single D2H */
 
@@ -63,23 +47,6 @@ static int check_system(const ParticleSystem* s) {
     if (s->count < 1 || !s->particles) {
         bhrt_set_err("particles: empty system (count %d, particles %s)", s->count,
                      s->particles ? "set" : "NULL");
-        return -1;
-    }
-    return 0;
-}
-
-static int check_object(const bhrt_particles* p) {
-    if (!p) {
-        bhrt_set_err("particles: NULL object");
-        return -1;
-    }
-    return 0;
-}
-
-static int check_device(const bhrt_particles* p) {
-    const int dev = bhrt_current_device();
-    if (dev != p->device) {
-        bhrt_set_err("particles: made on device %d, the current device is %d", p->device, dev);
         return -1;
     }
     return 0;
@@ -224,11 +191,6 @@ static int up_body(devctx_t* c, hipStream_t st, const void* arg) {
         return -1;
     }
     return 0;
-}
-
-static void used_on(bhrt_particles* p, devctx_t* c, hipStream_t stream) {
-    p->last = stream ? stream : c->stream;
-    p->used = 1;
 }
 
 int bhrt_particles_update_device(bhrt_particles* p, const BlackHoleParams* bh,
